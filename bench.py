@@ -13,9 +13,16 @@ One "step" = one full map: binning + deposit + (N > 1) RCCL reduce + ratio.  Wit
 the component maps are double-buffered so the reduce of map i runs on RCCL's stream while
 map i + 1 is binned and deposited (``--no-pipeline``: one map at a time).
 
-Run:  python bench.py [--gpus N --steps K --warmup W]
+Run:  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
       torchrun --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (the roofline is of the
+timed steps' own HIP events).  ``--full`` adds what takes runs of its own: the output check,
+the CPU baseline, the per-stage breakdown, the single-map latency, the two-stream
+'overlapped' region and the VALU roofline's pair counts.  ``--dump-outputs DIR`` writes the
+last timed step's arrays as DIR/<name>.npy (dump_outputs); the inputs are seeded, so two
+builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -119,11 +126,50 @@ def parse():
     ap.add_argument("--no-stage-events", dest="stage_events", action="store_false",
                     help="diagnostic: no per-stage HIP events in the timed region (no roofline)")
     ap.add_argument("--quiet", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything beside the headline figure: the "
+                         "output check, the CPU baseline, the per-stage breakdown, the "
+                         "single-map latency, the overlapped second timed region, the VALU "
+                         "roofline's pair counts (runs of their own).  Without it the run "
+                         "sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to "
+                         "DIR/<name>.npy (float32 / float64; at most 64 MB in all: larger "
+                         "arrays as a fixed, seeded sample of their elements)")
     return ap.parse_args()
 
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_MAX_BYTES = 60_000_000  # of array data: the files' headers stay well inside 64 MB
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: ``arrays`` ({name: tensor or None}, what the last timed step returned)
+    as path/<name>.npy, float64 tensors as float64 and everything else as float32.  All of
+    them whole when they fit DUMP_MAX_BYTES together; otherwise every array above its equal
+    share of the budget is written as a sample of its flattened elements: one element from
+    each of k equal strata, at offsets drawn from numpy's default_rng(0) -- the same
+    indices for the same shape in every run and every build."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+    size = lambda v: v.numel() * (8 if v.dtype == torch.float64 else 4)  # noqa: E731
+    share = DUMP_MAX_BYTES // max(1, len(arrays))
+    fits = sum(size(v) for v in arrays.values()) <= DUMP_MAX_BYTES
+    for name, v in arrays.items():
+        if v.dtype != torch.float64:
+            v = v.float()
+        if not fits and size(v) > share:
+            k = share // v.element_size()
+            n = v.numel()
+            idx = np.arange(k, dtype=np.int64) * n // k
+            idx += np.random.default_rng(0).integers(0, n // k, size=k)
+            v = v.contiguous().view(-1)[torch.from_numpy(idx).to(v.device)]
+        np.save(os.path.join(path, name + ".npy"), v.cpu().numpy())
 
 
 def chunk_cull_counts(pos, h, grid, cs, extent):
@@ -327,7 +373,11 @@ def run_cube(args, world, rank, local, dev):
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
-    ok = bool(torch.isfinite(out).all().item()) and float(out.abs().sum().item()) > 0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"cube": out})
+    ok = None
+    if args.full:
+        ok = bool(torch.isfinite(out).all().item()) and float(out.abs().sum().item()) > 0
     if rank != 0:
         if world > 1:
             dist.destroy_process_group()
@@ -337,7 +387,7 @@ def run_cube(args, world, rank, local, dev):
     dom_ms = prof[dom][0] / max(1, prof[dom][1])
     bytes_alg = args.n * 20 + C ** 3 * 4  # x, y, z, h, m + the cube (SURVEY §8(d) cfg 5)
     pairs = None
-    if dom in COMPUTE_BOUND:  # untimed: the exact voxel pairs (indicator cube, summed)
+    if args.full and dom in COMPUTE_BOUND:  # untimed: the exact voxel pairs (indicator cube, summed)
         cnt = project3d(x, y, z, h, torch.ones_like(h), cube_size=(C, C, C), extent=ext,
                         kernel="indicator", planes=(K[rank], K[rank + 1]))
         pairs = float(cnt.double().sum().item())
@@ -360,7 +410,7 @@ def run_cube(args, world, rank, local, dev):
                      "traffic": None, "bytes_alg_per_launch": bytes_alg},
         "stages": {k: {"ms_per_launch": ms / n, "launches": n} for k, (ms, n) in prof.items()},
         "records_per_particle": round(st["records"] / max(1, n_local), 4),
-        "work_items": st["items"], "output_ok": ok,
+        "work_items": st["items"], **({"output_ok": ok} if args.full else {}),
     }
     if pairs is not None:  # compute-bound: the VALU roofline, the HBM one beside it
         F = 11 + SHAPE_FLOPS[kernel] + 2  # dx, dy, dz (3), r^2 (5), sqrt, q, shape, a W
@@ -407,22 +457,27 @@ def run_stage(args, dev):
     torch.cuda.synchronize()
     t = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        out = step()
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t) / args.steps * 1e3
+    if args.dump_outputs:
+        su, sv, sh, sp = out
+        dump_outputs(args.dump_outputs, {"u": su, "v": sv, "h": sh,
+                                         **{f"prop{i}": p for i, p in enumerate(sp)}})
     bytes_alg = n * (24 + 3 * 8 + 5 * 4)
-    m = min(n, 1 << 24)
-    hp = [x[:m].cpu().numpy() for x in (pos, h, a0, a1)]
-    stage_particles(*hp, projection_axis=2)
-    torch.cuda.synchronize()
-    t = time.perf_counter()
-    stage_particles(*hp, projection_axis=2)
-    torch.cuda.synchronize()
-    host_s = time.perf_counter() - t
-    t = time.perf_counter()
-    f32 = [np.ascontiguousarray(hp[0][:, 0], np.float32), np.ascontiguousarray(hp[0][:, 1], np.float32)]
-    f32 += [np.ascontiguousarray(x, np.float32) for x in hp[1:]]
-    cpu_s = time.perf_counter() - t
+    if args.full:
+        m = min(n, 1 << 24)
+        hp = [x[:m].cpu().numpy() for x in (pos, h, a0, a1)]
+        stage_particles(*hp, projection_axis=2)
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        stage_particles(*hp, projection_axis=2)
+        torch.cuda.synchronize()
+        host_s = time.perf_counter() - t
+        t = time.perf_counter()
+        f32 = [np.ascontiguousarray(hp[0][:, 0], np.float32), np.ascontiguousarray(hp[0][:, 1], np.float32)]
+        f32 += [np.ascontiguousarray(x, np.float32) for x in hp[1:]]
+        cpu_s = time.perf_counter() - t
     res = {
         "metric": "staged particles/s (snapshot fp64 -> device fp32 SoA)", "value": n / ms * 1e3,
         "unit": "particles/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -434,12 +489,15 @@ def run_stage(args, dev):
                      "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(bytes_alg / ms / 1e6 / HBM_PEAK_GBS, 4), "traffic": None,
                      "bytes_alg_per_launch": bytes_alg},
-        "host_path": {"particles": m, "seconds": round(host_s, 4),
-                      "GB_per_s_pcie_inclusive": round(m * 48 / host_s / 1e9, 2)},
-        "cpu_baseline": {"value": m / cpu_s, "unit": "particles/s", "cores": 1, "kind": "port",
-                         "sample": f"NumPy column select + astype(float32) of {m} particles "
-                                   "(the host-side conversion create_image performs)"},
     }
+    if args.full:
+        res["host_path"] = {"particles": m, "seconds": round(host_s, 4),
+                            "GB_per_s_pcie_inclusive": round(m * 48 / host_s / 1e9, 2)}
+        res["cpu_baseline"] = {"value": m / cpu_s, "unit": "particles/s", "cores": 1,
+                               "kind": "port",
+                               "sample": f"NumPy column select + astype(float32) of {m} "
+                                         "particles (the host-side conversion create_image "
+                                         "performs)"}
     print(json.dumps(res), flush=True)
 
 
@@ -477,39 +535,42 @@ def run_knn(args, dev):
     ms = (time.perf_counter() - t) / args.steps * 1e3
     prof = {k: v for k, v in _lib.profile_read(local).items() if v[1]}
     _lib.profile(local, False)
-    ok = bool(torch.isfinite(h).all().item()) and float(h.min().item()) > 0
-    # untimed: the distances the search evaluates (one atomic per lane while counting)
-    os.environ["ASP_KNN_COUNT"] = "1"
-    try:
-        h2 = knn_smoothing_lengths(pos, 32)
-        torch.cuda.synchronize()
-        st = stats(local)
-    finally:
-        del os.environ["ASP_KNN_COUNT"]
-    same = bool(torch.equal(h, h2))
-    # window (fp32), cell scans (fp64), the shared cell pass's entries (fp32, every lane)
-    e32, e64 = float(st["evals"]), float(st["evals_small"])
-    eshared = float(st["evals_gather"]) * 64
-    e32 += eshared
-    s_ms = prof["knn_search"][0] / max(1, prof["knn_search"][1]) if "knn_search" in prof else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"h": h})
     roof = None
-    if s_ms:
-        t_peak = (e32 * DIST_FLOPS / (VALU_PEAK_TFLOPS * 1e12)
-                  + e64 * DIST_FLOPS / (VALU_F64_PEAK_TFLOPS * 1e12))
-        flops = (e32 + e64) * DIST_FLOPS
-        roof = {"bound": "valu", "kernel": "knn_search",
-                "achieved": round(flops / (s_ms * 1e-3) / 1e12, 3),
-                "peak": round(flops / t_peak / 1e12, 3), "unit": "TFLOP/s",
-                "frac": round(t_peak / (s_ms * 1e-3), 4),
-                "distances_fp32": int(e32), "distances_fp64": int(e64),
-                "distances_shared_pass": int(eshared),
-                "topk_insertions_per_particle": round(float(st["evals_wide"]) / args.n, 1),
-                "distances_per_particle": round((e32 + e64) / args.n, 1),
-                "flops_per_distance": DIST_FLOPS,
-                "kernel_ms_per_step": round(s_ms, 4),
-                "peak_note": f"work-weighted peak: fp32 distances at {VALU_PEAK_TFLOPS}, fp64 "
-                             f"at {VALU_F64_PEAK_TFLOPS} TFLOP/s; frac = time at those peaks "
-                             f"/ the search kernel's event time"}
+    if args.full:
+        ok = bool(torch.isfinite(h).all().item()) and float(h.min().item()) > 0
+        # untimed: the distances the search evaluates (one atomic per lane while counting)
+        os.environ["ASP_KNN_COUNT"] = "1"
+        try:
+            h2 = knn_smoothing_lengths(pos, 32)
+            torch.cuda.synchronize()
+            st = stats(local)
+        finally:
+            del os.environ["ASP_KNN_COUNT"]
+        same = bool(torch.equal(h, h2))
+        # window (fp32), cell scans (fp64), the shared cell pass's entries (fp32, every lane)
+        e32, e64 = float(st["evals"]), float(st["evals_small"])
+        eshared = float(st["evals_gather"]) * 64
+        e32 += eshared
+        s_ms = prof["knn_search"][0] / max(1, prof["knn_search"][1]) if "knn_search" in prof else None
+        if s_ms:
+            t_peak = (e32 * DIST_FLOPS / (VALU_PEAK_TFLOPS * 1e12)
+                      + e64 * DIST_FLOPS / (VALU_F64_PEAK_TFLOPS * 1e12))
+            flops = (e32 + e64) * DIST_FLOPS
+            roof = {"bound": "valu", "kernel": "knn_search",
+                    "achieved": round(flops / (s_ms * 1e-3) / 1e12, 3),
+                    "peak": round(flops / t_peak / 1e12, 3), "unit": "TFLOP/s",
+                    "frac": round(t_peak / (s_ms * 1e-3), 4),
+                    "distances_fp32": int(e32), "distances_fp64": int(e64),
+                    "distances_shared_pass": int(eshared),
+                    "topk_insertions_per_particle": round(float(st["evals_wide"]) / args.n, 1),
+                    "distances_per_particle": round((e32 + e64) / args.n, 1),
+                    "flops_per_distance": DIST_FLOPS,
+                    "kernel_ms_per_step": round(s_ms, 4),
+                    "peak_note": f"work-weighted peak: fp32 distances at {VALU_PEAK_TFLOPS}, fp64 "
+                                 f"at {VALU_F64_PEAK_TFLOPS} TFLOP/s; frac = time at those peaks "
+                                 f"/ the search kernel's event time"}
     res = {
         "metric": "k-NN smoothing lengths/s (k = 32, fp64, bit-exact vs scipy KDTree)",
         "value": args.n / ms * 1e3, "unit": "particles/s", "n_gpus": 1, "steps": args.steps,
@@ -518,11 +579,11 @@ def run_knn(args, dev):
         "data": "synthetic Plummer sphere (a=1, seed 0) generated in HBM",
         "config": {"workload": f"knn: {args.n:.0e} particles, k = 32", "particles": args.n},
         "stages": {k: {"ms_per_launch": a / b, "launches": b} for k, (a, b) in prof.items()},
-        "output_ok": ok and same,
+        **({"output_ok": ok and same} if args.full else {}),
     }
     if roof is not None:
         res["roofline"] = roof
-    if args.cpu_baseline != "off":
+    if args.full and args.cpu_baseline != "off":
         from scipy.spatial import KDTree
         m = min(args.n, 1 << 20)
         sample = pos[torch.randperm(args.n, device=dev)[:m]].cpu().numpy()
@@ -575,17 +636,20 @@ def run_ion(args, dev):
         out = step()
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t) / args.steps * 1e3
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"ion_mass": out})
     bytes_alg = n * 40
-    k = min(n, 1 << 16)
-    chk = out[:k].cpu().numpy()
-    s_h = state[:k].cpu().numpy()
-    from scipy.interpolate import RegularGridInterpolator
-    rgi = RegularGridInterpolator(axes, table, bounds_error=False, fill_value=-np.inf)
-    P = np.empty((k, 3))
-    P[:, :2] = s_h
-    P[:, 2] = z
-    want = (m[:k].cpu().numpy() * X[:k].cpu().numpy()) * 10.0 ** rgi(P)
-    ok = bool(np.allclose(chk, want, rtol=4.5e-16, atol=0))
+    if args.full:
+        k = min(n, 1 << 16)
+        chk = out[:k].cpu().numpy()
+        s_h = state[:k].cpu().numpy()
+        from scipy.interpolate import RegularGridInterpolator
+        rgi = RegularGridInterpolator(axes, table, bounds_error=False, fill_value=-np.inf)
+        P = np.empty((k, 3))
+        P[:, :2] = s_h
+        P[:, 2] = z
+        want = (m[:k].cpu().numpy() * X[:k].cpu().numpy()) * 10.0 ** rgi(P)
+        ok = bool(np.allclose(chk, want, rtol=4.5e-16, atol=0))
     res = {
         "metric": "ion masses/s (m * X * f_ion from a 3-D ionisation table, fp64)",
         "value": n / ms * 1e3, "unit": "particles/s", "n_gpus": 1, "steps": args.steps,
@@ -598,9 +662,9 @@ def run_ion(args, dev):
                      "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(bytes_alg / ms / 1e6 / HBM_PEAK_GBS, 4), "traffic": None,
                      "bytes_alg_per_launch": bytes_alg},
-        "output_ok": ok,
+        **({"output_ok": ok} if args.full else {}),
     }
-    if args.cpu_baseline != "off":
+    if args.full and args.cpu_baseline != "off":
         c = min(n, 1 << 22)
         s_c = state[:c].cpu().numpy()
         mc, Xc = m[:c].cpu().numpy(), X[:c].cpu().numpy()
@@ -831,10 +895,12 @@ def main():
     # (1.25e7: 0.618 -> 0.538 ms gated, profiles/r05/seq_main/).  The second, overlapped
     # region runs on one GPU only: at N > 1 the timed region itself already overlaps maps.
     ns = args.streams if args.streams > 0 else (1 if world == 1 else 2)
-    nso = args.overlap_streams if (args.overlap_streams > 1 and world == 1) else 0
+    nso_arg = args.overlap_streams if (args.overlap_streams > 1 and world == 1) else 0
+    nso = nso_arg if args.full else 0  # the second region itself: --full only
     mode = {"ns": ns, "streams": stream_set(ns)}
     gated = set_gate(ns)
-    nbuf = max(ns, nso, 2 if (world > 1 and args.pipeline) else 1)
+    # (the buffers of a --full run either way: the timed region is the same in both)
+    nbuf = max(ns, nso_arg, 2 if (world > 1 and args.pipeline) else 1)
     bufs = [torch.empty((2 if a1 is not None else 1, G, G), dtype=torch.float32, device=dev)
             for _ in range(nbuf)]
     pending = [None]
@@ -950,6 +1016,21 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t
     out0, out1 = last[0]
+
+    def whole_map(o0, o1):
+        """--decomp rows: the gathered row slabs -> the full map (rank 0; every rank: "all")"""
+        if R is None:
+            return o0, o1
+        if args.rows_gather == "all":
+            o0 = torch.cat([o0[r * rmax:r * rmax + R[r + 1] - R[r]] for r in range(world)])
+        elif rank != 0:
+            o0 = o0[R[rank]:R[rank + 1]]  # (the rest of its buffer was never written)
+        return o0, None
+
+    if args.dump_outputs and rank == 0:  # before any later region reuses the buffers
+        m0, m1 = whole_map(out0, out1)
+        dump_outputs(args.dump_outputs, {"map0": m0, "map1": m1})
+        del m0, m1
     prof = _lib.profile_read(local)  # timed region: the dominant stage's events
     _lib.profile(local, False)
     launched = {k: v for k, v in prof.items() if v[1]}
@@ -960,7 +1041,7 @@ def main():
     # N > 1: the single-map LATENCY as well (each map's collective completed before the
     # next map starts), beside the overlapped throughput of the timed region
     latency_ms = None
-    if nbuf > 1:
+    if args.full and nbuf > 1:
         k_lat = max(1, min(args.steps, 5))
         if world > 1:
             dist.barrier()
@@ -977,26 +1058,23 @@ def main():
         out0, out1 = last[0]
     st = stats(local)
     valu = None
-    if dom in COMPUTE_BOUND:
+    if args.full and dom in COMPUTE_BOUND:
         valu = pair_work(u, v, h, G, ext, args.kernel, world, dev)
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     # reduce_scatter: out0 / out1 are this rank's reduced row slab (ratio formed there)
-    if R is not None:  # the gathered row slabs -> the full map (rank 0; every rank: "all")
-        if args.rows_gather == "all":
-            out0 = torch.cat([out0[r * rmax:r * rmax + R[r + 1] - R[r]] for r in range(world)])
-        elif rank != 0:
-            out0 = out0[R[rank]:R[rank + 1]]  # (the rest of its buffer was never written)
-        out1 = None
-    ok = output_check(out0, out1, a0, a1, ratio, world,
-                      gathered_ratio=world > 1 and (args.op == "reduce_scatter_gather"
-                                                    or R is not None))
+    ok = None
+    if args.full:
+        out0, out1 = whole_map(out0, out1)
+        ok = output_check(out0, out1, a0, a1, ratio, world,
+                          gathered_ratio=world > 1 and (args.op == "reduce_scatter_gather"
+                                                        or R is not None))
     # the per-stage breakdown: a separate region of maps with every stage marked (untimed)
     k_bd = max(1, min(args.steps, 10))
     breakdown = {}
-    if args.stage_events:
+    if args.full and args.stage_events:
         drain()
         torch.cuda.synchronize()
         _lib.profile(local, True)
@@ -1034,13 +1112,7 @@ def main():
         if world > 1:
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el_o = float(tt.item())
-        o0, o1 = last[0]
-        if R is not None:
-            if args.rows_gather == "all":
-                o0 = torch.cat([o0[r * rmax:r * rmax + R[r + 1] - R[r]] for r in range(world)])
-            elif rank != 0:
-                o0 = o0[R[rank]:R[rank + 1]]
-            o1 = None
+        o0, o1 = whole_map(*last[0])
         ok_o = output_check(o0, o1, a0, a1, ratio, world,
                             gathered_ratio=world > 1 and (args.op == "reduce_scatter_gather"
                                                           or R is not None))
@@ -1145,12 +1217,13 @@ def main():
                          "the CUs and HBM; pipeline_frac (the whole map per step) is the "
                          "measure of the overlapped pipeline"} if ns > 1 else {})},
         **({"overlapped": overlapped} if overlapped else {}),
-        "stages": stages,
-        "stages_note": f"per-stage HIP-event times of {k_bd} further maps after the timed region "
-                       "(every stage marked); the timed region marks only the roofline's kernel",
+        **({"stages": stages,
+            "stages_note": f"per-stage HIP-event times of {k_bd} further maps after the timed "
+                           "region (every stage marked); the timed region marks only the "
+                           "roofline's kernel"} if args.full else {}),
         "records_per_particle": round(st["records"] / max(1, n_local), 4),
         "work_items": st["items"], "wide_particles": st["wide"], "large_records": st["large"],
-        "output_ok": ok,
+        **({"output_ok": ok} if args.full else {}),
     }
     if valu is not None:  # compute-bound regime: the VALU roofline, the HBM one beside it
         res["roofline_hbm"] = res["roofline"]
@@ -1167,7 +1240,8 @@ def main():
             if world > 1:
                 dist.destroy_process_group()
             sys.exit(4)
-    want_cpu = args.cpu_baseline == "on" or (args.cpu_baseline == "auto" and world == 1)
+    want_cpu = args.full and (args.cpu_baseline == "on"
+                              or (args.cpu_baseline == "auto" and world == 1))
     if want_cpu:
         try:
             res["cpu_baseline"] = cpu_baseline(args, extent)

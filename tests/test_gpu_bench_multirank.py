@@ -25,7 +25,7 @@ def _run(extra):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py",
            "--gpus", "2", "--particles", "2000000", "--grid", "1024", "--steps", "3", "--warmup", "1",
-           "--cpu-baseline", "off", "--quiet"] + extra
+           "--cpu-baseline", "off", "--quiet", "--full"] + extra
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

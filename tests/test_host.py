@@ -215,6 +215,39 @@ def test_bench_n_gt_1_defaults(monkeypatch):
     assert a.decomp == "zslab" and a.op == "reduce" and a.rows_gather == "all"
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: small arrays whole (float64 kept, the rest as float32, None
+    left out); arrays above the budget as the same sorted, duplicate-free sample of their
+    elements on every call; --full and --dump-outputs are off by default."""
+    import importlib.util
+    import sys
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(REPO, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1"])
+    a = b.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 2
+    x = torch.arange(1000, dtype=torch.float32).reshape(10, 100)
+    y = torch.arange(7, dtype=torch.float64)
+    b.dump_outputs(str(tmp_path / "a"), {"x": x, "y": y, "none": None})
+    assert sorted(os.listdir(tmp_path / "a")) == ["x.npy", "y.npy"]
+    gx, gy = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "a" / "y.npy")
+    assert gx.dtype == np.float32 and gx.shape == (10, 100) and np.array_equal(gx, x.numpy())
+    assert gy.dtype == np.float64 and np.array_equal(gy, y.numpy())
+    monkeypatch.setattr(b, "DUMP_MAX_BYTES", 4000)  # x (4000 B) + z (8000 B) no longer fit
+    z = torch.arange(1000, dtype=torch.float64) * 0.5
+    for d in ("b", "c"):
+        b.dump_outputs(str(tmp_path / d), {"x": x, "z": z})
+    sx, sz = np.load(tmp_path / "b" / "x.npy"), np.load(tmp_path / "b" / "z.npy")
+    assert sx.dtype == np.float32 and sz.dtype == np.float64
+    assert sx.nbytes + sz.nbytes <= 4000 and sx.size == 500 and sz.size == 250
+    assert np.all(np.diff(sx) > 0) and np.all(np.diff(sz) > 0)  # elements of x / z, no repeats
+    assert np.all(sx == np.round(sx)) and sx.max() < 1000 and np.all(sz * 2 == np.round(sz * 2))
+    assert np.array_equal(sx, np.load(tmp_path / "c" / "x.npy"))
+    assert np.array_equal(sz, np.load(tmp_path / "c" / "z.npy"))
+
+
 def test_row_slabs_group_needs_u():
     """A group member passing u=None would skip the all-reduce the others join (a hang);
     it is refused instead."""
