@@ -428,14 +428,46 @@ __device__ __forceinline__ f2 pk_one_minus_clamp(f2 q) {
     return d;
 }
 
-template <int KID>
-__device__ __forceinline__ f2 edge_shape2(f2 q) {
+// The dead zone at the kernel's edge.  The edge forms take no decision, so a pixel the
+// reference excludes (exact r >= 2h) whose fp32 q rounds below 2 -- a pixel at exactly
+// r = 2h is enough: v_rcp_f32(h) may round down -- would get t = 1 - q/2 > 0 and a term of
+// ~1e-20 W(0): nothing as a value, but a pixel with no neighbour at all must be EXACTLY 0
+// (DESIGN.md §5).  Such a pixel has t <= tau, tau bounding the fp32 error of q/2 for the
+// record; t^2 is formed as clamp(t t - tau^2), the same single packed fma-class
+// instruction as the product, so every t <= tau gives exactly 0 and every other term moves
+// by tau^2 t <= tau^2 of the peak (tau ~ 1e-4 at pixel-scale h: 1e-8, a sixth of an fp32
+// ulp; smaller for larger h).  nt2 = -tau^2 in both halves (0: no dead zone).
+// UNIFORM: nt2 is wave-uniform and read straight from its SGPR pair (the 2-D gather's
+// entries; a per-lane nt2, the cube's lane-per-record walk, needs VGPRs).
+template <bool UNIFORM = false>
+__device__ __forceinline__ f2 pk_square_dead(f2 t, f2 nt2) {
+    f2 d;
+    if constexpr (UNIFORM)
+        asm("v_pk_fma_f32 %0, %1, %1, %2 clamp" : "=v"(d) : "v"(t), "s"(nt2));
+    else
+        asm("v_pk_fma_f32 %0, %1, %1, %2 clamp" : "=v"(d) : "v"(t), "v"(nt2));
+    return d;
+}
+
+// -tau^2 of a 2-D record from its decision band (lo = thr - band, hi = thr + band,
+// set_band): an excluded pair has fp32 r2 >= thr - band, so q/2 >= 1 - band / (2 thr) and
+// t <= band / (2 thr); the gather forms q in units of h (three more roundings of 2^-24
+// and v / h, a coordinate rounding the band's margin covers) -- tau takes band / (2 thr)
+// plus 2^-20.  An infinite band (negative h) or one no smaller than the threshold itself
+// leaves the dead zone off.
+__device__ __forceinline__ float edge_dead2(float lo, float hi) {
+    const float tau = 0.5f * (hi - lo) * __builtin_amdgcn_rcpf(hi + lo) + 0x1p-20f;
+    return tau < 0x1p-4f ? -(tau * tau) : 0.0f;
+}
+
+template <int KID, bool UNIFORM = false>
+__device__ __forceinline__ f2 edge_shape2(f2 q, f2 nt2) {
     const f2 t = pk_one_minus_half_clamp(q);
+    const f2 t2 = pk_square_dead<UNIFORM>(t, nt2);
     if constexpr (KID == 0) {
         const f2 s = pk_one_minus_clamp(q);
-        return __builtin_elementwise_fma((f2){-0.5f, -0.5f}, s * s * s, t * t * t);
+        return __builtin_elementwise_fma((f2){-0.5f, -0.5f}, s * s * s, t2 * t);
     } else {
-        const f2 t2 = t * t;
         return (t2 * t2) * __builtin_elementwise_fma((f2){2.0f, 2.0f}, q, (f2){1.0f, 1.0f});
     }
 }

@@ -1156,8 +1156,9 @@ __device__ __forceinline__ unsigned block_hits(unsigned box, const GOwn& o) {
 // Edge-continuous kernels (cubic / Wendland) on a square grid without a mixed cull take no
 // decision at all (gather_entry_masked below): W by edge_shape for every pixel of every
 // 8 x 16 half block row the entry's disc reaches.  A pixel the reference excludes has
-// exact r >= 2h, so its fp32 q is >= 2 (1 - 2^-21) and its term 0 or < 2^-60 W(0); one it
-// includes the same way.
+// exact r >= 2h, so its fp32 t = 1 - q/2 lies inside the entry's dead zone (edge_dead2,
+// asp_device.hpp) and its term is exactly 0; one it includes inside the dead zone loses a
+// term below tau^3 W(0).
 
 // One (uniform) entry, every other case: the box's own rows and columns (non-square grids
 // and mixed culls clip the box to the chunk ranges), the error band and the fp64
@@ -1200,9 +1201,10 @@ __device__ __forceinline__ void gather_entry(const Grid& g, const Src64& s, cons
 // One (uniform) entry of the edge path given its half-row mask bm (edge_mask).
 template <int KID, int NOUT, int ACC>
 __device__ __forceinline__ void gather_entry_masked(float u, float vs, float hinv, float s0,
-                                                    float s1, unsigned bm, const GCorner& c,
-                                                    GAcc<NOUT, ACC>& ga) {
+                                                    float s1, float nt2, unsigned bm,
+                                                    const GCorner& c, GAcc<NOUT, ACC>& ga) {
     const f2 hv = {-hinv, -hinv};
+    const f2 dead = {nt2, nt2};  // the entry's dead zone at q = 2 (edge_dead2)
     const f2 vv = {vs, vs};
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
@@ -1217,7 +1219,7 @@ __device__ __forceinline__ void gather_entry_masked(float u, float vs, float hin
                     f2 q;
                     q.x = __builtin_amdgcn_sqrtf(r2.x);
                     q.y = __builtin_amdgcn_sqrtf(r2.y);
-                    ga.add2(2 * r + k, edge_shape2<KID>(q), s0, s1);
+                    ga.add2(2 * r + k, edge_shape2<KID, true>(q, dead), s0, s1);
                 }
             }
         }
@@ -1234,13 +1236,18 @@ __device__ __forceinline__ void gather_walk(const Grid& g, const Src64& s, const
         // v / h; the walk then reads 6 words per entry and tests mask bits
         const unsigned em = mine.box == kNoBox ? 0u : edge_mask(c, mine.u, mine.v, mine.hi);
         const float vs = mine.v * mine.hinv;
+        // the entry's dead zone (-tau^2, edge_dead2) rides in the mask word, the mask in its
+        // low 4 mantissa bits (2^-19 of tau^2, far inside tau's own 2^-20 margin): the walk
+        // reads one word per entry for both
+        const unsigned emd = em | (__float_as_uint(edge_dead2(mine.lo, mine.hi)) & ~15u);
         unsigned long long m = __ballot(em != 0u);
         while (m) {
             const int l = __builtin_ctzll(m);
             m &= m - 1;
+            const unsigned w = (unsigned)bcast((int)emd, l);
             gather_entry_masked<KID, NOUT, ACC>(bcast(mine.u, l), bcast(vs, l), bcast(mine.hinv, l),
                                                 bcast(mine.s0, l), bcast(mine.s1, l),
-                                                (unsigned)bcast((int)em, l), c, ga);
+                                                __uint_as_float(w), w & 15u, c, ga);
         }
     } else {
         unsigned long long m = __ballot(meets_region(mine.box, o));

@@ -391,10 +391,11 @@ struct Rec3 {
 };
 
 // Edge-continuous kernels (cubic, Wendland) take no per-voxel decision (as the 2-D gather,
-// DESIGN.md §3): edge_shape2 (asp_device.hpp) gives exactly 0 for q >= 2, evaluated in fp32
-// from fp32 plane offsets, two planes per packed instruction, so a voxel whose exact test
-// differs contributes < 2^-60 W(0).  The indicator kernel keeps the fp64 test (bit-exact
-// voxel counts).
+// DESIGN.md §3): edge_shape2 (asp_device.hpp) gives exactly 0 for q >= 2 (1 - tau), evaluated
+// in fp32 from fp32 plane offsets, two planes per packed instruction, with tau the record's
+// bound on the fp32 error of q/2 (col_consts): a voxel the oracle excludes gets exactly 0,
+// one it includes inside that dead zone loses a term below tau^3 W(0).  The indicator kernel
+// keeps the fp64 test (bit-exact voxel counts).
 
 // One (i, j) column of a record's box.  The oracle's test is
 //   r2 = dx * dx + dy * dy + dz * dz  <  (2h)^2      (voxel_pass, left to right in fp64)
@@ -445,8 +446,8 @@ __device__ __forceinline__ void voxel3(const Rec3& R, double s, int li, int lj, 
 // sc = the term coefficient x kShapeScale.
 template <int KID>
 __device__ __forceinline__ void plane_walk(double* col, float fa, float fb, float sfh, float zh,
-                                           float pzh, float sc) {
-    const f2 zr2 = {zh, zh}, npz = {pzh, pzh}, sf2 = {sfh, sfh};
+                                           float pzh, float sc, float nt2) {
+    const f2 zr2 = {zh, zh}, npz = {pzh, pzh}, sf2 = {sfh, sfh}, dead = {nt2, nt2};
     const f2 sc2 = {sc, sc}, sc22 = {2.0f * sc, 2.0f * sc};
     auto planes2 = [&](f2 pl) {
         const f2 dz = __builtin_elementwise_fma(pl, npz, zr2);
@@ -454,10 +455,10 @@ __device__ __forceinline__ void plane_walk(double* col, float fa, float fb, floa
         const f2 q = f2{__builtin_amdgcn_sqrtf(r2.x), __builtin_amdgcn_sqrtf(r2.y)};
         if constexpr (KID == 1) {  // Wendland C2: c t^4 (1 + 2q) = t^4 (c + 2c q)
             const f2 t = pk_one_minus_half_clamp(q);
-            const f2 t2 = t * t;
+            const f2 t2 = pk_square_dead(t, dead);
             return (t2 * t2) * __builtin_elementwise_fma(sc22, q, sc2);
         } else {
-            return edge_shape2<KID>(q) * sc2;
+            return edge_shape2<KID>(q, dead) * sc2;
         }
     };
     // whole plane pairs, no odd last plane: a column of odd length also adds plane fb + 1,
@@ -485,6 +486,7 @@ struct ColE {
     float rzs;       // 1 / pz (1 + 2^-18)
     float kc, k0f, k1f;
     float h2, zh, pzh, sc;
+    float nt2;       // -tau^2: the dead zone at q = 2 (pk_square_dead, asp_device.hpp)
 };
 template <int KID>
 __device__ __forceinline__ ColE col_consts(const Grid3& g, const Rec3& R) {
@@ -499,6 +501,13 @@ __device__ __forceinline__ ColE col_consts(const Grid3& g, const Rec3& R) {
     K.zh = R.zr * R.hinv;
     K.pzh = -(float)g.pz * R.hinv;
     K.sc = R.s * kShapeScale<KID>;
+    // tau bounds the fp32 error of q/2 at the sphere's surface: the offsets lx, ly, zr and
+    // up to 15 stepped subtractions per axis (<= 2^-24 (32 h + 31 pitches) each of x and y,
+    // 2^-24 (11 h + 288 pz) for z through zh and 32 pzh), the fmas, hinv^2 and the sqrt
+    // (15 x 2^-24 relative): <= 2^-24 (45 + 175 pitch / h); taken as 2^-18 + 2^-16 pitch / h
+    const float pmax = fmaxf(fmaxf((float)g.px, (float)g.py), (float)g.pz);
+    const float tau = fmaf(0x1p-16f * pmax, fabsf(R.hinv), 0x1p-18f);
+    K.nt2 = tau < 0x1p-4f ? -(tau * tau) : 0.0f;
     return K;
 }
 
@@ -516,7 +525,7 @@ __device__ __forceinline__ void column_e(const ColE& K, double* col, float sf) {
     const float fa = __builtin_amdgcn_fmed3f(ceilf(K.kc - rz), K.k0f, 0x1p30f);
     const float fb = __builtin_amdgcn_fmed3f(floorf(K.kc + rz), -0x1p30f, K.k1f);
     if (!(fa <= fb)) return;
-    plane_walk<KID>(col, fa, fb, sf * K.h2, K.zh, K.pzh, K.sc);
+    plane_walk<KID>(col, fa, fb, sf * K.h2, K.zh, K.pzh, K.sc, K.nt2);
 }
 
 template <int KID>
@@ -751,6 +760,7 @@ __global__ __launch_bounds__(kDBlock) void k3_deposit(Grid3 g, const float4* __r
                         K.zh = bcast(Kl.zh, l);
                         K.pzh = bcast(Kl.pzh, l);
                         K.sc = bcast(Kl.sc, l);
+                        K.nt2 = bcast(Kl.nt2, l);
                         const float lx = bcast(R.lx, l), ly = bcast(R.ly, l);
                         const int i0 = bcast(R.b.i0, l), j0 = bcast(R.b.j0, l);
                         const int qw = bcast(bw, l), qh = bcast(bh, l);

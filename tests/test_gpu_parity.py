@@ -7,6 +7,8 @@ Bars (stated here):
     |g - r| <= 2e-5 * max|r|   everywhere, and
     |g - r| <= 1e-4 * |r|      where |r| >= 1e-3 * max|r|;
   pixels where the reference is exactly 0 are exactly 0.
+This global-peak bar is kept for the golden vectors; the values of each deposit path are
+pinned per pixel in tests/test_gpu_path_values.py (tests/value_bar.py).
 """
 import numpy as np
 import pytest
