@@ -1,6 +1,6 @@
 // asp_device.hpp -- device-side building blocks of the projector (gfx950 / CDNA4).
 //
-// Reference semantics restated here (paths under /root/reference/src/astro_sph_tools/):
+// Reference semantics restated here (paths under the reference's src/astro_sph_tools/):
 //   pixel corner        tools/projections/_pixel_calculations.pyx:11-14
 //   neighbour test      tools/projections/_pixel_calculations.pyx:30-31  (r2 < (2h)^2)
 //   chunk (tile) cull   tools/projections/_projector.py:34-48

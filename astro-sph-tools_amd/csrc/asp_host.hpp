@@ -5,10 +5,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <mutex>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/asp.h"
@@ -28,6 +31,40 @@ inline int fail(int code, const std::string& msg) {
         if (e_ != hipSuccess)                                                            \
             return fail(ASP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
+
+#define ASP_TRY(expr)                  \
+    do {                               \
+        int rc_ = (expr);              \
+        if (rc_ != ASP_OK) return rc_; \
+    } while (0)
+
+// Environment knobs (tuning, A/B switches, test hooks): every read goes through these two.
+// env_int: the variable's integer value clamped to [lo, hi], or def when it is not set.
+// Knobs are read on every call (tests change them mid-process) unless the caller keeps
+// the value in a function static.
+inline long long env_int(const char* name, long long def, long long lo = INT_MIN,
+                         long long hi = INT_MAX) {
+    const char* e = getenv(name);
+    return e ? std::max(lo, std::min(hi, atoll(e))) : def;
+}
+inline bool env_set(const char* name) { return getenv(name) != nullptr; }
+
+// Runtime (kernel id, map count, deterministic) -> compile-time constants: calls
+// f(Int<KID>, Int<NOUT>, Int<ACC>) with ACC = 0 (fp64 sums) / 1 (fixed point), the values of
+// kAccF64 / kAccFix.  f is a generic lambda; only the combinations named here instantiate.
+template <int V>
+using Int = std::integral_constant<int, V>;
+template <class F>
+inline int dispatch_kid(int kid, F&& f) {
+    return kid == 0 ? f(Int<0>{}) : kid == 1 ? f(Int<1>{}) : f(Int<2>{});
+}
+template <class F>
+inline int dispatch(int kid, int nout, bool det, F&& f) {
+    return dispatch_kid(kid, [&](auto K) {
+        if (nout == 1) return det ? f(K, Int<1>{}, Int<1>{}) : f(K, Int<1>{}, Int<0>{});
+        return det ? f(K, Int<2>{}, Int<1>{}) : f(K, Int<2>{}, Int<0>{});
+    });
+}
 
 struct Buf {
     void* p = nullptr;
@@ -176,10 +213,7 @@ struct SlotTable {
 inline SlotTable g_slots[64];
 inline Workspace& slot_ws(int device, int s) { return s == 0 ? g_ws[device] : g_ws_alt[device][s - 1]; }
 inline int map_slot(int device, hipStream_t st) {
-    static const int nslots = [] {
-        const char* e = getenv("ASP_MAP_SLOTS");
-        return e ? std::max(1, std::min(kMapSlots, atoi(e))) : kMapSlots;
-    }();
+    static const int nslots = (int)env_int("ASP_MAP_SLOTS", kMapSlots, 1, kMapSlots);
     SlotTable& T = g_slots[device];
     std::lock_guard<std::mutex> lock(T.mu);
     int s = -1;
@@ -205,10 +239,7 @@ struct DepositGate {
     hipStream_t st = nullptr;
 };
 inline DepositGate g_gate[64];
-inline bool scatter_gate_on() {
-    const char* e = getenv("ASP_SCATTER_GATE");
-    return e && atoi(e) != 0;
-}
+inline bool scatter_gate_on() { return env_int("ASP_SCATTER_GATE", 0) != 0; }
 inline int gate_wait(int device, hipStream_t st) {  // before a map's scatter
     DepositGate& G = g_gate[device];
     std::lock_guard<std::mutex> lock(G.mu);
@@ -336,15 +367,9 @@ inline int ensure(Buf& b, size_t bytes) {
                                        hipGetErrorString(e));
     }
     b.cap = want;
-    if (getenv("ASP_PRINT_ALLOC")) fprintf(stderr, "asp alloc %zu B at %p\n", want, b.p);
+    if (env_set("ASP_PRINT_ALLOC")) fprintf(stderr, "asp alloc %zu B at %p\n", want, b.p);
     return ASP_OK;
 }
-
-#define ASP_TRY(expr)                  \
-    do {                               \
-        int rc_ = (expr);              \
-        if (rc_ != ASP_OK) return rc_; \
-    } while (0)
 
 // Dynamic LDS above the 64 KiB default: the kernel's attribute is raised once per (kernel,
 // device) to at least `bytes`, under a lock -- calls may run on several threads (one per
@@ -388,10 +413,9 @@ inline int place_records(Workspace& ws, size_t bytes, hipStream_t st, F&& scatte
                          int* ntrials = nullptr) {
     placed = false;
     if (ntrials) *ntrials = 0;
-    const char* e = getenv("ASP_PLACEMENT_TRIALS");
-    const int trials = e ? std::max(0, atoi(e)) : 16;
-    const char* mb = getenv("ASP_PLACEMENT_MIN_MB");  // tests lower it
-    if (trials < 2 || bytes < ((size_t)(mb ? atoi(mb) : 256) << 20)) return ASP_OK;
+    const int trials = (int)env_int("ASP_PLACEMENT_TRIALS", 16, 0);
+    const size_t min_mb = (size_t)env_int("ASP_PLACEMENT_MIN_MB", 256);  // tests lower it
+    if (trials < 2 || bytes < (min_mb << 20)) return ASP_OK;
     hipEvent_t t0, t1;
     ASP_HIP(hipEventCreate(&t0));
     ASP_HIP(hipEventCreate(&t1));
@@ -430,7 +454,7 @@ inline int place_records(Workspace& ws, size_t bytes, hipStream_t st, F&& scatte
             (void)hipFree(cand.p);  // the best still holds this call's records from its run
             ws.recs = best;
         }
-        if (getenv("ASP_PRINT_ALLOC"))
+        if (env_set("ASP_PRINT_ALLOC"))
             fprintf(stderr, "asp placement trial %d: %.3f ms (best %.3f)\n", t, ms, best_ms);
     }
     (void)hipEventDestroy(t0);
@@ -438,6 +462,92 @@ inline int place_records(Workspace& ws, size_t bytes, hipStream_t st, F&& scatte
     if (ntrials) *ntrials = runs;
     placed = rc == ASP_OK;
     return rc;
+}
+
+// ----------------------------------------------------------------------------------
+// Pieces of the count -> scans -> counter read-back -> scatter sequence that the 2-D map
+// (project2d_device) and the cube (cube_pass) share; each pipeline calls them in order.
+// ----------------------------------------------------------------------------------
+constexpr int kRetSplit = 1;  // internal: >= 2^31 records in one pass; the caller splits
+// The capacity a scatter launched AFTER the read-back is given: no pass that gets that far
+// has more records (record_limit), so it never declines.
+constexpr long long kNoRecordCap = 0x7fffffffLL;
+
+// The device counters, zeroed on st, and their pinned host mirror.
+inline int counters_begin(Workspace& ws, int ncounters, hipStream_t st) {
+    ASP_TRY(ensure(ws.counters, (size_t)ncounters * sizeof(int)));
+    if (!ws.h_counters)
+        ASP_HIP(hipHostMalloc((void**)&ws.h_counters, kMarks * ncounters * sizeof(int)));
+    ASP_HIP(hipMemsetAsync(ws.counters.p, 0, (size_t)ncounters * sizeof(int), st));
+    return ASP_OK;
+}
+
+// Records are 32 B (two float4); record cursors are 32-bit (ASP_MAX_RECORDS: tests).
+inline size_t record_bytes(long long n_recs) { return (size_t)n_recs * 32; }
+inline long long record_limit() { return env_int("ASP_MAX_RECORDS", 0x7fffffffLL, 1, LLONG_MAX); }
+// Records the buffer left by an earlier call holds: what a speculative scatter, enqueued
+// before the host has the counters, checks them against.  < 2^31 - 1: the tilescan's
+// clamped record count always exceeds it when it overflows.
+inline long long record_capacity(const Workspace& ws) {
+    return (long long)std::min<size_t>(ws.recs.cap / 32, 0x7ffffffe);
+}
+inline bool speculate_on() { return !env_set("ASP_NO_SPECULATE"); }
+
+// With the counters on the host: kRetSplit when the pass makes too many records (nothing
+// is kept), else pre = the speculative scatter did the work.  One that did not (it
+// returned at once, or its records are discarded) is waited for, so that the buffers it
+// was given can be re-allocated.
+inline int settle_speculation(bool spec, long long n_recs, bool fits, hipStream_t st, bool& pre) {
+    const bool split = n_recs >= record_limit();
+    pre = spec && fits && !split;
+    if (spec && !pre) ASP_HIP(hipStreamSynchronize(st));
+    return split ? kRetSplit : ASP_OK;
+}
+
+// The record buffer grown to n_recs records; fresh: it was re-allocated, so its placement
+// is worth trials (place_records).
+inline int ensure_records(Workspace& ws, long long n_recs, bool& fresh) {
+    const void* before = ws.recs.p;
+    ASP_TRY(ensure(ws.recs, record_bytes(n_recs)));
+    fresh = ws.recs.p != before;
+    return ASP_OK;
+}
+
+// Particles per pipeline pass: particle indices and record cursors are 32-bit, so larger
+// calls run as batches accumulating into the same output (ASP_MAX_BATCH lowers it for
+// tests).  pass(a, b, i) runs particles [a, b) as the i-th pass that completes; a batch
+// whose pass returns kRetSplit is halved and tried again.  The caller accumulates for
+// i > 0 and forms a ratio only after the last pass (b - a < n: there are several).
+template <class F>
+inline int for_batches(long long n, F&& pass) {
+    const long long B = env_int("ASP_MAX_BATCH", 1LL << 30, 1, LLONG_MAX);
+    std::vector<std::pair<long long, long long>> todo;  // batches, last first
+    for (long long a = ((n - 1) / B) * B; a >= 0; a -= B) todo.push_back({a, std::min(n, a + B)});
+    for (int i = 0; !todo.empty();) {
+        const auto [a, b] = todo.back();
+        todo.pop_back();
+        const int rc = pass(a, b, i);
+        if (rc == kRetSplit) {
+            if (b - a < 2) return fail(ASP_ERR_UNSUPPORTED, "one particle makes >= 2^31 records");
+            todo.push_back({a + (b - a) / 2, b});
+            todo.push_back({a, a + (b - a) / 2});
+            continue;
+        }
+        ASP_TRY(rc);
+        ++i;
+    }
+    return ASP_OK;
+}
+
+// asp_last_stats reads slot 0's words: a call clears its workspace's, fills in what it
+// measures and, when it ran in another slot, publishes them -- under slot 0's lock, since a
+// slot-0 call on another thread writes the same words (no cycle: slot-0 calls never take
+// another slot's lock).
+inline void stats_clear(Workspace& ws) { std::fill(ws.stats, ws.stats + kNStats, 0LL); }
+inline void stats_publish(Workspace& ws, int device) {
+    if (&ws == &g_ws[device]) return;
+    std::lock_guard<std::mutex> lk(g_ws[device].mu);
+    std::copy(ws.stats, ws.stats + kNStats, g_ws[device].stats);
 }
 
 #define ASP_LAUNCHED()                                                                    \

@@ -1265,7 +1265,7 @@ static int knn(const double* pos, long long n, int k, double* h, int flags, int 
         ASP_LAUNCHED();
     }
     // sub-tables of the dense level-L cells: at most n / (kSubMin + 1) of them
-    const int submin = getenv("ASP_KNN_SUBMIN") ? std::max(8, atoi(getenv("ASP_KNN_SUBMIN"))) : kSubMin;
+    const int submin = (int)env_int("ASP_KNN_SUBMIN", kSubMin, 8);
     const long long nslot_max = n / (submin + 1) + 1;
     ASP_TRY(ensure(ws.knn[8], (size_t)(ncell + 1) * sizeof(int)));
     ASP_TRY(ensure(ws.knn[9], (size_t)nslot_max * (kSubCells + 1) * sizeof(int)));
@@ -1284,25 +1284,25 @@ static int knn(const double* pos, long long n, int k, double* h, int flags, int 
     mprep.done();
     // diagnostics only: ASP_KNN_THREAD = one lane per particle throughout;
     // ASP_KNN_DIAG = 1: the window pass alone (wrong results, timing)
-    const bool per_thread = getenv("ASP_KNN_THREAD") != nullptr;
-    const int diag = getenv("ASP_KNN_DIAG") ? atoi(getenv("ASP_KNN_DIAG")) : 0;
-    const int whalf = getenv("ASP_KNN_WINDOW") ? atoi(getenv("ASP_KNN_WINDOW")) : kWinHalf;
-    const int fine = getenv("ASP_KNN_FINE") ? atoi(getenv("ASP_KNN_FINE")) : kCellFine;
-    const int f32 = getenv("ASP_KNN_F32") ? atoi(getenv("ASP_KNN_F32")) : kWindowF32;
+    const bool per_thread = env_set("ASP_KNN_THREAD");
+    const int diag = (int)env_int("ASP_KNN_DIAG", 0);
+    const int whalf = (int)env_int("ASP_KNN_WINDOW", kWinHalf);
+    const int fine = (int)env_int("ASP_KNN_FINE", kCellFine);
+    const int f32 = (int)env_int("ASP_KNN_F32", kWindowF32);
     // the shared cell pass: the common level covers uq / 64 of a wave's lanes (0: off)
     // the window / shared passes' entry test: 16 entries per step into a bit mask (1) or
     // one entry per step into an 8-slot buffer (0)
-    const bool mask = getenv("ASP_KNN_MASK") ? atoi(getenv("ASP_KNN_MASK")) != 0 : kMaskTest;
+    const bool mask = env_int("ASP_KNN_MASK", kMaskTest) != 0;
     // the window pass's chunk order: nearest to the wave's own first (1) or in array order (0)
-    const int near = getenv("ASP_KNN_NEAR") ? atoi(getenv("ASP_KNN_NEAR")) : kNearFirst;
+    const int near = (int)env_int("ASP_KNN_NEAR", kNearFirst);
     // the window's first k entries sorted into the empty top-k (k == 32 / 64 only)
-    const int fill = getenv("ASP_KNN_FILL") ? atoi(getenv("ASP_KNN_FILL")) : 1;
-    const int uq = getenv("ASP_KNN_UNION") ? std::min(64, std::max(0, atoi(getenv("ASP_KNN_UNION")))) : kUnionQ;
+    const int fill = (int)env_int("ASP_KNN_FILL", 1);
+    const int uq = (int)env_int("ASP_KNN_UNION", kUnionQ, 0, 64);
     // ASP_KNN_COUNT: count the distances the search evaluates (bench.py's k-NN roofline;
     // one atomic per lane, so off in timed runs) -> asp_last_stats [9] window, [10] cells,
     // [11] entries the shared cell pass streamed (once per wave), [12] top-k insertions
     unsigned long long* evc = nullptr;
-    if (getenv("ASP_KNN_COUNT")) {
+    if (env_set("ASP_KNN_COUNT")) {
         ASP_TRY(ensure(ws.knn[11], 8 * sizeof(unsigned long long)));
         evc = (unsigned long long*)ws.knn[11].p;
         ASP_HIP(hipMemsetAsync(evc, 0, 8 * sizeof(unsigned long long), st));
@@ -1335,7 +1335,7 @@ static int knn(const double* pos, long long n, int k, double* h, int flags, int 
 #undef ASP_KNN
     ASP_LAUNCHED();
     msearch.done();
-    for (int j = 9; j <= 12; ++j) ws.stats[j] = 0;
+    stats_clear(ws);  // (the map counters describe the last map no longer)
     if (evc) {
         unsigned long long e[8];
         ASP_HIP(hipMemcpyAsync(e, evc, sizeof(e), hipMemcpyDeviceToHost, st));
@@ -1344,7 +1344,7 @@ static int knn(const double* pos, long long n, int k, double* h, int flags, int 
         ws.stats[10] = (long long)e[1];
         ws.stats[11] = (long long)e[2];
         ws.stats[12] = (long long)e[3];
-        if (getenv("ASP_KNN_COUNT_PRINT"))
+        if (env_set("ASP_KNN_COUNT_PRINT"))
             fprintf(stderr, "knn shared pass: %llu waves, %.1f columns and %.1f ranges per wave\n", e[6],
                     e[6] ? (double)e[4] / e[6] : 0.0, e[6] ? (double)e[5] / e[6] : 0.0);
     }
@@ -1352,6 +1352,7 @@ static int knn(const double* pos, long long n, int k, double* h, int flags, int 
         ASP_HIP(hipMemcpyAsync(h, dh, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
         ASP_HIP(hipStreamSynchronize(st));
     }
+    stats_publish(ws, device);
     return ws_end_.finish();
 }
 

@@ -1,7 +1,7 @@
 // asp_project2d.hip -- MI355X (gfx950) SPH particle -> pixel-grid projection.
 //
 // Replaces the reference's create_image / process_chunk / calculate_pixel_value /
-// quartic_spline_kernel path (/root/reference/src/astro_sph_tools/tools/projections/
+// quartic_spline_kernel path (the reference's src/astro_sph_tools/tools/projections/
 // _projector.py:13-120, _pixel_calculations.pyx:9-36, _kernels.pyx:9-20) with a
 // scatter formulation built for CDNA4:
 //
@@ -209,26 +209,10 @@ __global__ __launch_bounds__(kCountBlock) void k_count(const float* __restrict__
 
 // Record stores of the scatter: plain stores (non-temporal ones measured 2x slower, the
 // L2 merges the 32-B halves of a line).
-// ASP_SCATTER_ABLATE (experiment builds only, never the default): 1 -- the record stores
-// become a store under a condition no record meets (the records are still formed), 2 -- as
-// 1 and the cursor claims become a plain index (no LDS atomics).  The deposit kernels then
-// return at once (the record buffer holds no records).  DESIGN.md §4, round 6.
-#ifndef ASP_SCATTER_ABLATE
-#define ASP_SCATTER_ABLATE 0
-#endif
-// batches of particle loads the scatter keeps in flight ahead of the one it bins (1, or 2
-// as an A/B build switch)
-#ifndef ASP_SCATTER_PREFETCH
-#define ASP_SCATTER_PREFETCH 1
-#endif
 __device__ __forceinline__ void rec_store(float4* dst, float4 v) {
     // one global_store_dwordx4 per half record: the empty asm keeps the vectorizer from
     // regrouping two halves as dwordx3 + unaligned dwordx4 + dword
-#if ASP_SCATTER_ABLATE
-    if (v.x == 1.25e-37f && v.y == -1.25e-37f) *dst = v;
-#else
     *dst = v;
-#endif
     asm volatile("" ::: "memory");
 }
 
@@ -382,16 +366,6 @@ __global__ __launch_bounds__(kScatterBlock) void k_scatter(
     load_all(c, pu, pv, ph, pa0, pa1);
     load_src(c, pU, pV);
     load_x(c, px);
-#if ASP_SCATTER_PREFETCH >= 2
-    // A/B build switch: the batch after next in flight as well
-    long long cmid = step_batch();
-    float mu[kLane], mv[kLane], mh[kLane], ma0[kLane], ma1[kLane];
-    load_all(cmid, mu, mv, mh, ma0, ma1);
-    double mU[kLane], mV[kLane];
-    load_src(cmid, mU, mV);
-    float mx_[NX ? 4 : 1][kLane];
-    load_x(cmid, mx_);
-#endif
     while (c < n) {
         const long long cn = step_batch();  // the next batch to load
         float nu[kLane], nv[kLane], nh[kLane], na0[kLane], na1[kLane];
@@ -446,11 +420,7 @@ __global__ __launch_bounds__(kScatterBlock) void k_scatter(
                 const int t = tx * g.nty + ty;
                 const unsigned bp = tile_box(b, tx, ty);
                 const int col = mb && box_large(bp, g) ? t + g.ntiles : t;
-#if ASP_SCATTER_ABLATE >= 2
-                int slot = col;
-#else
                 int slot = atomicAdd(&cur[col], 1);
-#endif
                 if constexpr (NX) rec_store(&xa.ext[slot], cx);
                 if constexpr (ACC == kAccFix) {
                     atomicMax(&cm[t * NOUT], c0);
@@ -504,25 +474,6 @@ __global__ __launch_bounds__(kScatterBlock) void k_scatter(
             __builtin_amdgcn_wave_barrier();
             first_slot[k] = -1;
         }
-#if ASP_SCATTER_PREFETCH >= 2
-#pragma unroll
-        for (int k = 0; k < kLane; ++k) {
-            pu[k] = mu[k], mu[k] = nu[k];
-            pv[k] = mv[k], mv[k] = nv[k];
-            ph[k] = mh[k], mh[k] = nh[k];
-            pa0[k] = ma0[k], ma0[k] = na0[k];
-            pa1[k] = ma1[k], ma1[k] = na1[k];
-            pU[k] = mU[k], mU[k] = nU[k];
-            pV[k] = mV[k], mV[k] = nV[k];
-        }
-        if constexpr (NX)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int k = 0; k < kLane; ++k) px[j][k] = mx_[j][k], mx_[j][k] = nx_[j][k];
-        c = cmid;
-        cmid = cn;
-#else
 #pragma unroll
         for (int k = 0; k < kLane; ++k) {
             pu[k] = nu[k];
@@ -539,7 +490,6 @@ __global__ __launch_bounds__(kScatterBlock) void k_scatter(
 #pragma unroll
                 for (int k = 0; k < kLane; ++k) px[j][k] = nx_[j][k];
         c = cn;
-#endif
     }
     __syncthreads();
     if constexpr (ACC == kAccFix) {
@@ -1310,9 +1260,6 @@ __global__ __launch_bounds__(kDepBlock) __attribute__((amdgpu_waves_per_eu(4))) 
     float* xt = (float*)(acc + NOUT * kTileWords);
     float* yt = xt + kTile;
     __shared__ int defer_lds[kDepBlock / 64][kDeferCap];
-#if ASP_SCATTER_ABLATE
-    return;
-#endif
     const Item it = items[order[blockIdx.x]];  // largest items first (k_tilescan)
     if (it.mode != 0) return;  // the large stream's (K4g)
     int tx = it.tile / g.nty, ty = it.tile - (it.tile / g.nty) * g.nty;
@@ -1442,9 +1389,6 @@ __global__ __launch_bounds__(kGatherThreads) void k_gather(
     unsigned long long* __restrict__ slabs, float* __restrict__ out0, float* __restrict__ out1,
     int flags, const float4* __restrict__ ext, int pass) {
     extern __shared__ __attribute__((aligned(16))) double tot[];
-#if ASP_SCATTER_ABLATE
-    return;
-#endif
     const Item it = items[order[blockIdx.x / kGatherRegions]];  // largest first
     if (it.mode != 1) return;
     const int tx = it.tile / g.nty, ty = it.tile - (it.tile / g.nty) * g.nty;
@@ -1492,9 +1436,6 @@ __global__ __launch_bounds__(kBlock) void k_merge(Grid g, const Merge* __restric
                                                   const int2* __restrict__ tile_k,
                                                   float* __restrict__ out0,
                                                   float* __restrict__ out1, int flags) {
-#if ASP_SCATTER_ABLATE
-    return;
-#endif
     const Merge m = merges[blockIdx.x];
     int tx = m.tile / g.nty, ty = m.tile - (m.tile / g.nty) * g.nty;
     int X0 = tx * kTile, Y0 = ty * kTile;
@@ -2006,7 +1947,7 @@ struct Plan {
 // two-stream overlap loses more than the split saves (1.25e7 share: 0.592 vs 0.540 ms), so
 // the one-launch scan is used there.  ASP_SPLIT_SCAN=0 / 1 forces either (read per call).
 static bool split_scan_on() {
-    if (const char* e = getenv("ASP_SPLIT_SCAN")) return atoi(e) != 0;
+    if (env_set("ASP_SPLIT_SCAN")) return env_int("ASP_SPLIT_SCAN", 0) != 0;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
     SlotTable& T = g_slots[dev];
@@ -2016,16 +1957,13 @@ static bool split_scan_on() {
     return true;
 }
 
-static int item_order_identity() {
-    static const int identity = [] {
-        const char* e = getenv("ASP_ITEM_ORDER");
-        return e && atoi(e) == 0 ? 1 : 0;
-    }();
+static int item_order_identity() {  // (read once per process)
+    static const int identity = env_int("ASP_ITEM_ORDER", 1) == 0 ? 1 : 0;
     return identity;
 }
-// deposit work items per map (ASP_ITEMS overrides kTargetItems2d; tuning only)
+// deposit work items per map (ASP_ITEMS overrides kTargetItems2d; tuning only, read once)
 static inline int item_target() {
-    static const int t = getenv("ASP_ITEMS") ? std::max(64, atoi(getenv("ASP_ITEMS"))) : kTargetItems2d;
+    static const int t = (int)env_int("ASP_ITEMS", kTargetItems2d, 64);
     return t;
 }
 static inline size_t item_cap(const Grid& g) { return (size_t)2 * g.ntiles + item_target() + kTargetItems1 + 16; }
@@ -2066,24 +2004,91 @@ static int launch_scatter(const Grid& g, const Src64& s, Workspace& ws, const Pl
                           bool probe = false, const XArgs* xa = nullptr) {
     StageMark m(ws, kSScatter, st);
     const XArgs none{};
-    int rc;
-#define ASP_SV(C, S, P, X) scatter_variant<KID, NOUT, ACC, C, S, P, X>(g, s, ws, pl, u, v, h, a0, a1, rec_cap, wide_cap, st, X ? *xa : none)
+    // (CULL, SRC) from the grid and the source arrays, for the given (PROBE, NX)
+    auto launch = [&](auto P, auto X) {
+        auto go = [&](auto C, auto S) {
+            constexpr int nx = decltype(X)::value;
+            return scatter_variant<KID, NOUT, ACC, decltype(C)::value, decltype(S)::value,
+                                   decltype(P)::value, nx>(g, s, ws, pl, u, v, h, a0, a1, rec_cap,
+                                                           wide_cap, st, nx ? *xa : none);
+        };
+        return g.nonsquare || g.mixed ? go(std::true_type{}, Int<2>{})
+               : s.u64                ? go(std::false_type{}, Int<1>{})
+                                      : go(std::false_type{}, Int<0>{});
+    };
+    bool done = false;
     if constexpr (NOUT == 2 && ACC == kAccF64) {
         if (xa) {
-            if (g.nonsquare || g.mixed) rc = ASP_SV(true, 2, 0, 1);
-            else if (s.u64) rc = ASP_SV(false, 1, 0, 1);
-            else rc = ASP_SV(false, 0, 0, 1);
-            ASP_TRY(rc);
-            m.done();
-            return ASP_OK;
+            ASP_TRY(launch(Int<0>{}, Int<1>{}));
+            done = true;
         }
     }
-    if (g.nonsquare || g.mixed) rc = probe ? ASP_SV(true, 2, 1, 0) : ASP_SV(true, 2, 0, 0);
-    else if (s.u64) rc = probe ? ASP_SV(false, 1, 1, 0) : ASP_SV(false, 1, 0, 0);
-    else rc = probe ? ASP_SV(false, 0, 1, 0) : ASP_SV(false, 0, 0, 0);
-#undef ASP_SV
-    ASP_TRY(rc);
+    if (!done) ASP_TRY(probe ? launch(Int<1>{}, Int<0>{}) : launch(Int<0>{}, Int<0>{}));
     m.done();
+    return ASP_OK;
+}
+
+static_assert(kAccF64 == 0 && kAccFix == 1, "dispatch() passes ACC as Int<0> / Int<1>");
+
+static inline unsigned stream_blocks(long long n) {  // grid of a grid-stride streaming kernel
+    return (unsigned)std::max<long long>(1, std::min<long long>((n + kBlock - 1) / kBlock, 8192));
+}
+
+static int launch_ratio(Workspace& ws, float* o0, const float* o1, long long npix, hipStream_t st) {
+    StageMark m(ws, kSRatio, st);
+    hipLaunchKernelGGL(k_ratio, dim3(stream_blocks(npix)), dim3(kBlock), 0, st, o0, o1, npix);
+    ASP_LAUNCHED();
+    m.done();
+    return ASP_OK;
+}
+
+// K4 / K4g / K5 / K6: the records in ws deposited into o0 (, o1).  EXT = 0: the records'
+// own two coefficients (a0 / a1: the properties' fp32 arrays, which the wide particles read
+// directly).  EXT = 1 (asp_project2d_props, pass = 1, 2): properties (2 pass, 2 pass + 1)
+// from the ext coefficients the pass-0 scatter wrote beside each record.
+template <int KID, int NOUT, int ACC, int EXT>
+static int run_deposit(const Grid& g, const Src64& s, Workspace& ws, const Plan& pl, const float* u,
+                       const float* v, const float* h, const float* a0, const float* a1, float* o0,
+                       float* o1, int dflags, hipStream_t st, int pass) {
+    const float4* recs = (const float4*)ws.recs.p;
+    const float4* ext = EXT ? (const float4*)ws.ext.p : nullptr;
+    const Item* items = (const Item*)ws.items.p;
+    const int* iorder = (const int*)ws.iorder.p;
+    const int2* tile_k = (const int2*)ws.tile_k.p;
+    unsigned long long* slabs = (unsigned long long*)ws.slabs.p;
+    {
+        StageMark m(ws, kSDeposit, st);
+        const size_t lds = deposit_lds<NOUT>();
+        ASP_TRY(allow_dyn_lds((const void*)k_deposit<KID, NOUT, ACC, EXT>, lds));
+        hipLaunchKernelGGL((k_deposit<KID, NOUT, ACC, EXT>), dim3(pl.n_items), dim3(kDepBlock), lds,
+                           st, g, s, recs, items, iorder, tile_k, slabs, o0, o1, dflags, ext, pass);
+        ASP_LAUNCHED();
+        m.done();
+    }
+    if (pl.n_large > 0) {
+        StageMark m(ws, kSGather, st);
+        hipLaunchKernelGGL((k_gather<KID, NOUT, ACC, EXT>), dim3(pl.n_items * kGatherRegions),
+                           dim3(kGatherThreads), (gather_lds<NOUT, ACC>()), st, g, s, recs, items,
+                           iorder, tile_k, slabs, o0, o1, dflags, ext, pass);
+        ASP_LAUNCHED();
+        m.done();
+    }
+    if (pl.n_merges > 0) {
+        StageMark m(ws, kSMerge, st);
+        hipLaunchKernelGGL((k_merge<NOUT, ACC>), dim3(pl.n_merges, kTilePix / kBlock), dim3(kBlock),
+                           0, st, g, (const Merge*)ws.merges.p, (const unsigned long long*)slabs,
+                           tile_k, o0, o1, dflags);
+        ASP_LAUNCHED();
+        m.done();
+    }
+    if (pl.n_wide > 0) {
+        StageMark m(ws, kSWide, st);
+        hipLaunchKernelGGL((k_wide<KID, NOUT, ACC>), dim3(g.ntiles * kGatherRegions),
+                           dim3(kGatherThreads), (gather_lds<NOUT, ACC>()), st, g, s, u, v, h, a0,
+                           a1, (const int*)ws.wide.p, pl.n_wide, (const int*)ws.counters.p, o0, o1);
+        ASP_LAUNCHED();
+        m.done();
+    }
     return ASP_OK;
 }
 
@@ -2093,14 +2098,12 @@ static int run_tail(const Grid& g, const Src64& s, Workspace& ws, const Plan& pl
                     const float* v, const float* h, const float* a0, const float* a1, float* o0,
                     float* o1, int flags, hipStream_t st, bool pre_scattered,
                     const XArgs* xa = nullptr) {
-    int* dc = (int*)ws.counters.p;
     const bool ratio = (flags & ASP_F_RATIO) != 0;
     const bool fuse_ratio = ratio && pl.n_wide == 0;
-    const unsigned long long* slabs = (const unsigned long long*)ws.slabs.p;
     const int dflags = ((flags & ASP_F_ACCUMULATE) ? kFlagAccumulate : 0) |
                        (fuse_ratio ? kFlagRatio : 0);
     if (!pre_scattered)
-        ASP_TRY((launch_scatter<KID, NOUT, ACC>(g, s, ws, pl, u, v, h, a0, a1, 0x7fffffffLL,
+        ASP_TRY((launch_scatter<KID, NOUT, ACC>(g, s, ws, pl, u, v, h, a0, a1, kNoRecordCap,
                                                 0x7fffffff, st, false, xa)));
     if (ACC == kAccFix) {
         StageMark m(ws, kSScale, st);
@@ -2110,115 +2113,16 @@ static int run_tail(const Grid& g, const Src64& s, Workspace& ws, const Plan& pl
         ASP_LAUNCHED();
         m.done();
     }
-    {
-        StageMark m(ws, kSDeposit, st);
-        const size_t lds = deposit_lds<NOUT>();
-        ASP_TRY(allow_dyn_lds((const void*)k_deposit<KID, NOUT, ACC>, lds));
-        hipLaunchKernelGGL((k_deposit<KID, NOUT, ACC>), dim3(pl.n_items), dim3(kDepBlock), lds, st, g, s, (const float4*)ws.recs.p,
-                           (const Item*)ws.items.p, (const int*)ws.iorder.p, (const int2*)ws.tile_k.p,
-                           (unsigned long long*)ws.slabs.p, o0, o1, dflags, (const float4*)nullptr, 0);
-        ASP_LAUNCHED();
-        m.done();
-    }
-    if (pl.n_large > 0) {
-        StageMark m(ws, kSGather, st);
-        const size_t lds = gather_lds<NOUT, ACC>();
-        hipLaunchKernelGGL((k_gather<KID, NOUT, ACC>), dim3(pl.n_items * kGatherRegions),
-                           dim3(kGatherThreads), lds, st, g,
-                           s, (const float4*)ws.recs.p, (const Item*)ws.items.p,
-                           (const int*)ws.iorder.p, (const int2*)ws.tile_k.p,
-                           (unsigned long long*)ws.slabs.p, o0, o1, dflags, (const float4*)nullptr, 0);
-        ASP_LAUNCHED();
-        m.done();
-    }
-    if (pl.n_merges > 0) {
-        StageMark m(ws, kSMerge, st);
-        hipLaunchKernelGGL((k_merge<NOUT, ACC>), dim3(pl.n_merges, kTilePix / kBlock), dim3(kBlock),
-                           0, st, g, (const Merge*)ws.merges.p, slabs, (const int2*)ws.tile_k.p,
-                           o0, o1, dflags);
-        ASP_LAUNCHED();
-        m.done();
-    }
-    if (pl.n_wide > 0) {
-        StageMark m(ws, kSWide, st);
-        const size_t lds = gather_lds<NOUT, ACC>();
-        hipLaunchKernelGGL((k_wide<KID, NOUT, ACC>), dim3(g.ntiles * kGatherRegions),
-                           dim3(kGatherThreads), lds, st, g, s,
-                           u, v, h, a0, a1, (const int*)ws.wide.p, pl.n_wide, (const int*)dc, o0,
-                           o1);
-        ASP_LAUNCHED();
-        m.done();
-    }
-    if (ratio && !fuse_ratio) {
-        long long npix = (long long)g.nx * g.ny;
-        long long blocks = std::min<long long>((npix + kBlock - 1) / kBlock, 8192);
-        StageMark m(ws, kSRatio, st);
-        hipLaunchKernelGGL(k_ratio, dim3((unsigned)std::max<long long>(1, blocks)), dim3(kBlock),
-                           0, st, o0, (const float*)o1, npix);
-        ASP_LAUNCHED();
-        m.done();
-    }
-    return ASP_OK;
-}
-
-// asp_project2d_props, pass p = 1, 2: properties (2p, 2p + 1) deposited from the records
-// the pass-0 map binned and their ext coefficients (K4 / K4g / K5 / K6 as in run_tail, fp64
-// accumulation, no ratio) into o0 (, o1; NOUT = 1 for an odd last property).  xa0 / xa1:
-// the properties' fp32 arrays (the wide particles read them directly).
-template <int KID, int NOUT>
-static int run_ext_pass(const Grid& g, const Src64& s, Workspace& ws, const Plan& pl,
-                        const float* u, const float* v, const float* h, const float* xa0,
-                        const float* xa1, float* o0, float* o1, int flags, hipStream_t st,
-                        int pass) {
-    int* dc = (int*)ws.counters.p;
-    const unsigned long long* slabs = (const unsigned long long*)ws.slabs.p;
-    const int dflags = (flags & ASP_F_ACCUMULATE) ? kFlagAccumulate : 0;
-    const float4* ext = (const float4*)ws.ext.p;
-    {
-        StageMark m(ws, kSDeposit, st);
-        ASP_TRY(allow_dyn_lds((const void*)k_deposit<KID, NOUT, kAccF64, 1>, deposit_lds<NOUT>()));
-        hipLaunchKernelGGL((k_deposit<KID, NOUT, kAccF64, 1>), dim3(pl.n_items), dim3(kDepBlock),
-                           deposit_lds<NOUT>(), st, g, s, (const float4*)ws.recs.p,
-                           (const Item*)ws.items.p, (const int*)ws.iorder.p,
-                           (const int2*)ws.tile_k.p, (unsigned long long*)ws.slabs.p, o0, o1,
-                           dflags, ext, pass);
-        ASP_LAUNCHED();
-        m.done();
-    }
-    if (pl.n_large > 0) {
-        StageMark m(ws, kSGather, st);
-        hipLaunchKernelGGL((k_gather<KID, NOUT, kAccF64, 1>), dim3(pl.n_items * kGatherRegions),
-                           dim3(kGatherThreads), (gather_lds<NOUT, kAccF64>()), st, g, s,
-                           (const float4*)ws.recs.p, (const Item*)ws.items.p,
-                           (const int*)ws.iorder.p, (const int2*)ws.tile_k.p,
-                           (unsigned long long*)ws.slabs.p, o0, o1, dflags, ext, pass);
-        ASP_LAUNCHED();
-        m.done();
-    }
-    if (pl.n_merges > 0) {
-        StageMark m(ws, kSMerge, st);
-        hipLaunchKernelGGL((k_merge<NOUT, kAccF64>), dim3(pl.n_merges, kTilePix / kBlock),
-                           dim3(kBlock), 0, st, g, (const Merge*)ws.merges.p, slabs,
-                           (const int2*)ws.tile_k.p, o0, o1, dflags);
-        ASP_LAUNCHED();
-        m.done();
-    }
-    if (pl.n_wide > 0) {
-        StageMark m(ws, kSWide, st);
-        hipLaunchKernelGGL((k_wide<KID, NOUT, kAccF64>), dim3(g.ntiles * kGatherRegions),
-                           dim3(kGatherThreads), (gather_lds<NOUT, kAccF64>()), st, g, s, u, v, h,
-                           xa0, xa1, (const int*)ws.wide.p, pl.n_wide, (const int*)dc, o0, o1);
-        ASP_LAUNCHED();
-        m.done();
-    }
+    ASP_TRY((run_deposit<KID, NOUT, ACC, 0>(g, s, ws, pl, u, v, h, a0, a1, o0, o1, dflags, st, 0)));
+    if (ratio && !fuse_ratio) ASP_TRY(launch_ratio(ws, o0, o1, (long long)g.nx * g.ny, st));
     return ASP_OK;
 }
 
 // Tunables read once per call (experiments; the defaults are the measured choices).
 static void grid_tunables(Grid& g) {
-    if (const char* e = getenv("ASP_WIDE_TILES")) g.wide_tiles = std::max(1, atoi(e));
-    if (const char* e = getenv("ASP_GATHER_MIN")) g.gather_min = std::max(2, atoi(e));
-    if (const char* e = getenv("ASP_GATHER_AREA")) g.gather_area = std::max(4, atoi(e));
+    g.wide_tiles = (int)env_int("ASP_WIDE_TILES", g.wide_tiles, 1);
+    g.gather_min = (int)env_int("ASP_GATHER_MIN", g.gather_min, 2);
+    g.gather_area = (int)env_int("ASP_GATHER_AREA", g.gather_area, 4);
 }
 
 // The projection on DEVICE arrays (fp32 working copies u, v, h, a0, a1; s: the caller's
@@ -2226,8 +2130,7 @@ static void grid_tunables(Grid& g) {
 // caller holds the workspace lock and has ordered st behind the previous call.
 // bin_only (the kernel_func plug-in session): stop after the scatter -- the records stay in
 // ws for k_pairs -- and return the number of wide particles there.
-constexpr int kRetSplit = 1;  // internal: >= 2^31 records in one pass, nothing written
-
+// Returns kRetSplit (nothing written) when the pass would make >= 2^31 records.
 // xa / nxp / xo (asp_project2d_props): nxp (1..4) further properties xa->a[0 ..] binned
 // with the first two (their coefficients beside each record) and deposited in further
 // passes into xo[0 ..] (two-map fp64 calls only).
@@ -2254,15 +2157,13 @@ int project2d_device(Workspace& ws, const Grid& gin, const Src64& s, const float
             for (int j = 0; j < nxp; ++j) ASP_HIP(hipMemsetAsync(xo[j], 0, npix * sizeof(float), st));
             m.done();
         }
-        for (long long& x : ws.stats) x = 0;
+        stats_clear(ws);
         return ASP_OK;
     }
     ASP_TRY(ensure_morton(ws, g.ntx, g.nty, st));
-    long long max_blk = kMaxBinBlocks;
-    if (const char* e = getenv("ASP_BIN_BLOCKS")) max_blk = std::max(1, atoi(e));
+    const long long max_blk = env_int("ASP_BIN_BLOCKS", kMaxBinBlocks, 1);
     pl.nblk = std::min<long long>(max_blk, std::max<long long>(1, (n + 8191) / 8192));
-    pl.grp = kScatterGroup;
-    if (const char* e = getenv("ASP_SCATTER_GROUP")) pl.grp = std::max(1, atoi(e));
+    pl.grp = (int)env_int("ASP_SCATTER_GROUP", kScatterGroup, 1);
     pl.nblk_s = (pl.nblk + pl.grp - 1) / pl.grp;
     const bool det = (flags & ASP_F_DETERMINISTIC) != 0;
     ASP_TRY(ensure(ws.hist, (size_t)pl.nblk * 2 * g.ntiles * sizeof(int)));
@@ -2273,10 +2174,8 @@ int project2d_device(Workspace& ws, const Grid& gin, const Src64& s, const float
     ASP_TRY(ensure(ws.items, item_cap(g) * sizeof(Item)));
     ASP_TRY(ensure(ws.iorder, item_cap(g) * sizeof(int)));  // deposit order (k_tilescan)
     ASP_TRY(ensure(ws.merges, merge_cap(g) * sizeof(Merge)));
-    ASP_TRY(ensure(ws.counters, (size_t)cNum * sizeof(int)));
-    if (!ws.h_counters) ASP_HIP(hipHostMalloc((void**)&ws.h_counters, kMarks * cNum * sizeof(int)));
+    ASP_TRY(counters_begin(ws, cNum, st));
     int* dc = (int*)ws.counters.p;
-    ASP_HIP(hipMemsetAsync(dc, 0, (size_t)cNum * sizeof(int), st));
     {
         StageMark m(ws, kSCount, st);
         hipLaunchKernelGGL(g.nonsquare || g.mixed ? k_count<true> : k_count<false>,
@@ -2318,7 +2217,8 @@ int project2d_device(Workspace& ws, const Grid& gin, const Src64& s, const float
     // left by an earlier call, the scatter is enqueued BEFORE the host waits for it
     // (speculatively: it checks the counters against those capacities itself), so the
     // GPU does not idle across the host round trip.  The copy runs on the side stream, so
-    // the scatter behind it on st need not wait for the copy's own latency.
+    // the scatter behind it on st need not wait for the copy's own latency (the cube's copy
+    // is on its own stream: it has no side kernel to follow).
     ASP_TRY(ensure_side(ws));
     ASP_HIP(hipEventRecord(ws.scan_ev, st));
     int gate_dev = -1;  // ASP_SCATTER_GATE: this map's scatter after the last map's deposit
@@ -2334,20 +2234,18 @@ int project2d_device(Workspace& ws, const Grid& gin, const Src64& s, const float
     ASP_HIP(hipMemcpyAsync(ws.h_counters, dc, (size_t)cNum * sizeof(int), hipMemcpyDeviceToHost,
                            ws.side));
     ASP_HIP(hipEventRecord(ws.cnt_ev, ws.side));
-    // < 2^31 - 1: the tilescan's clamped record count always exceeds it when it overflows
-    const long long rec_cap = (long long)std::min<size_t>(ws.recs.cap / (2 * sizeof(float4)), 0x7ffffffe);
+    const long long rec_cap = record_capacity(ws);
     const int wide_cap = (int)std::min<size_t>(ws.wide.cap / sizeof(int), 0x7fffffff);
-    const bool spec = ws.recs.p && ws.wide.p && !xa && getenv("ASP_NO_SPECULATE") == nullptr;
-    if (spec) {
-#define ASP_SC(K, N, A) \
-    launch_scatter<K, N, A>(g, s, ws, pl, du, dv, dh, da0, da1, rec_cap, wide_cap, st)
-#define ASP_SC2(K, A) (nout == 1 ? ASP_SC(K, 1, A) : ASP_SC(K, 2, A))
-#define ASP_SC3(A) (kid == 0 ? ASP_SC2(0, A) : kid == 1 ? ASP_SC2(1, A) : ASP_SC2(2, A))
-        ASP_TRY(det ? ASP_SC3(kAccFix) : ASP_SC3(kAccF64));
-#undef ASP_SC3
-#undef ASP_SC2
-#undef ASP_SC
-    }
+    // every scatter of this pass: the kernel for (kid, nout, det), given capacities, PROBE
+    auto scatter = [&](long long rcap, int wcap, bool probe) {
+        return dispatch(kid, nout, det, [&](auto K, auto N, auto A) {
+            return launch_scatter<K(), N(), A()>(g, s, ws, pl, du, dv, dh, da0, da1, rcap, wcap,
+                                                 st, probe);
+        });
+    };
+    // (not with extra properties: their coefficient array is sized from the counters)
+    const bool spec = ws.recs.p && ws.wide.p && !xa && speculate_on();
+    if (spec) ASP_TRY(scatter(rec_cap, wide_cap, false));
     ASP_HIP(hipEventSynchronize(ws.cnt_ev));
     if (split) ASP_HIP(hipStreamWaitEvent(st, ws.cnt_ev, 0));  // the deposit reads part 2's output
     const int* hc = ws.h_counters;
@@ -2357,16 +2255,11 @@ int project2d_device(Workspace& ws, const Grid& gin, const Src64& s, const float
     pl.n_slabs = hc[cSlabs];
     pl.n_wide = hc[cWideCount];
     pl.n_large = hc[cLarge];
-    long long rec_limit = 0x7fffffffLL;  // 32-bit record cursors (ASP_MAX_RECORDS: tests)
-    if (const char* e = getenv("ASP_MAX_RECORDS")) rec_limit = std::max(1LL, atoll(e));
-    if (pl.n_recs >= rec_limit) {  // nothing written yet: the caller splits the batch
-        if (spec) ASP_HIP(hipStreamSynchronize(st));  // its (no-op) scatter is done
-        return kRetSplit;
-    }
-    const bool pre = spec && pl.n_recs <= rec_cap && pl.n_wide <= wide_cap;
-    if (spec && !pre) ASP_HIP(hipStreamSynchronize(st));  // its (no-op) scatter is done
-    const void* recs_before = ws.recs.p;
-    ASP_TRY(ensure(ws.recs, (size_t)pl.n_recs * 2 * sizeof(float4)));
+    bool pre = false;  // the speculative scatter did the work
+    ASP_TRY(settle_speculation(spec, pl.n_recs, pl.n_recs <= rec_cap && pl.n_wide <= wide_cap, st,
+                               pre));
+    bool fresh = false;
+    ASP_TRY(ensure_records(ws, pl.n_recs, fresh));
     ASP_TRY(ensure(ws.wide, (size_t)pl.n_wide * sizeof(int)));
     ASP_TRY(ensure(ws.slabs, (size_t)pl.n_slabs * nout * kTilePix * sizeof(long long)));
     XArgs xw{};
@@ -2377,55 +2270,44 @@ int project2d_device(Workspace& ws, const Grid& gin, const Src64& s, const float
     }
     bool placed = false;  // the records are already scattered (by the placement trials)
     int ntrials = 0;      // scatter runs of the placement trials
-    if (!bin_only && !xa && !pre && ws.recs.p != recs_before) {
-#define ASP_SC(K, N, A) \
-    launch_scatter<K, N, A>(g, s, ws, pl, du, dv, dh, da0, da1, 0x7fffffffLL, 0x7fffffff, st, true)
-#define ASP_SC2(K, A) (nout == 1 ? ASP_SC(K, 1, A) : ASP_SC(K, 2, A))
-#define ASP_SC3(A) (kid == 0 ? ASP_SC2(0, A) : kid == 1 ? ASP_SC2(1, A) : ASP_SC2(2, A))
-        auto scatter = [&]() -> int {
+    // (plain maps only: not the plug-in session's binning, nor a scatter that also writes
+    // the extra properties' ws.ext)
+    if (!bin_only && !xa && !pre && fresh) {
+        auto trial = [&]() -> int {
             // the wide-list cursor is the one counter the scatter advances
             ASP_HIP(hipMemsetAsync(dc + cWideCursor, 0, sizeof(int), st));
-            return det ? ASP_SC3(kAccFix) : ASP_SC3(kAccF64);
+            return scatter(kNoRecordCap, 0x7fffffff, true);
         };
-#undef ASP_SC3
-#undef ASP_SC2
-#undef ASP_SC
-        ASP_TRY(place_records(ws, (size_t)pl.n_recs * 2 * sizeof(float4), st, scatter, placed,
-                              &ntrials));
+        ASP_TRY(place_records(ws, record_bytes(pl.n_recs), st, trial, placed, &ntrials));
     }
-    const bool pre_all = pre || placed;
     if (bin_only) {  // the plugin session: the records, for k_pairs
         if (!pre)
-            ASP_TRY((launch_scatter<2, 1, kAccF64>(g, s, ws, pl, du, dv, dh, da0, da1, 0x7fffffffLL,
+            ASP_TRY((launch_scatter<2, 1, kAccF64>(g, s, ws, pl, du, dv, dh, da0, da1, kNoRecordCap,
                                                    0x7fffffff, st)));
         *bin_only = pl.n_wide;
         return ASP_OK;
     }
-    int rc;
     const XArgs* xp = xa ? &xw : nullptr;
-#define ASP_TAIL(K, N, A) \
-    run_tail<K, N, A>(g, s, ws, pl, du, dv, dh, da0, da1, d0, d1, flags, st, pre_all, xp)
-#define ASP_TAIL2(K, A) (nout == 1 ? ASP_TAIL(K, 1, A) : ASP_TAIL(K, 2, A))
-#define ASP_TAIL3(A) (kid == 0 ? ASP_TAIL2(0, A) : kid == 1 ? ASP_TAIL2(1, A) : ASP_TAIL2(2, A))
-    rc = det ? ASP_TAIL3(kAccFix) : ASP_TAIL3(kAccF64);
-#undef ASP_TAIL3
-#undef ASP_TAIL2
-#undef ASP_TAIL
-    if (rc != ASP_OK) return rc;
-    for (int pass = 1; xa && 2 * (pass - 1) < nxp; ++pass) {  // properties 2.. from the records
-        const int j = 2 * (pass - 1);
+    ASP_TRY(dispatch(kid, nout, det, [&](auto K, auto N, auto A) {
+        return run_tail<K(), N(), A()>(g, s, ws, pl, du, dv, dh, da0, da1, d0, d1, flags, st,
+                                       pre || placed, xp);
+    }));
+    for (int j = 0; xa && j < nxp; j += 2) {  // properties 2.. from the records, two per pass
         const bool two = j + 1 < nxp;
-        float* o1x = two ? xo[j + 1] : nullptr;
-        const int xflags = flags & ASP_F_ACCUMULATE;
-#define ASP_XP(K) (two ? run_ext_pass<K, 2>(g, s, ws, pl, du, dv, dh, xw.a[j], xw.a[j + 1], xo[j], o1x, xflags, st, pass) \
-                       : run_ext_pass<K, 1>(g, s, ws, pl, du, dv, dh, xw.a[j], xw.a[j], xo[j], o1x, xflags, st, pass))
-        rc = kid == 0 ? ASP_XP(0) : kid == 1 ? ASP_XP(1) : ASP_XP(2);
-#undef ASP_XP
-        if (rc != ASP_OK) return rc;
+        const int dflags = (flags & ASP_F_ACCUMULATE) ? kFlagAccumulate : 0;
+        ASP_TRY(dispatch_kid(kid, [&](auto K) {  // (fp64 sums only: check_props)
+            auto go = [&](auto N) {
+                return run_deposit<K(), N(), kAccF64, 1>(g, s, ws, pl, du, dv, dh, xw.a[j],
+                                                         xw.a[two ? j + 1 : j], xo[j],
+                                                         two ? xo[j + 1] : nullptr, dflags, st,
+                                                         j / 2 + 1);
+            };
+            return two ? go(Int<2>{}) : go(Int<1>{});
+        }));
     }
     if (gate_dev >= 0) ASP_TRY(gate_record(gate_dev, st));
-    for (int k = 9; k <= 12; ++k) ws.stats[k] = 0;  // the evals diagnostic of THIS pass only
-    if (getenv("ASP_COUNT_EVALS")) {  // diagnostic: the deposit kernels' lane-slots
+    stats_clear(ws);  // (the evals diagnostic below is of THIS pass only)
+    if (env_set("ASP_COUNT_EVALS")) {  // diagnostic: the deposit kernels' lane-slots
         ASP_TRY(ensure(ws.aux[5], 3 * sizeof(unsigned long long)));
         ASP_HIP(hipMemsetAsync(ws.aux[5].p, 0, 3 * sizeof(unsigned long long), st));
         hipLaunchKernelGGL(k_evals, dim3((unsigned)(pl.n_items + (pl.n_wide ? g.ntiles : 0))),
@@ -2459,14 +2341,6 @@ int project2d_device(Workspace& ws, const Grid& gin, const Src64& s, const float
     return ASP_OK;
 }
 
-// Particles per pipeline pass: particle indices and record cursors are 32-bit, so larger
-// calls run as batches accumulating into the same maps (ASP_MAX_BATCH lowers it for tests).
-static long long max_batch() {
-    long long b = 1LL << 30;
-    if (const char* e = getenv("ASP_MAX_BATCH")) b = std::max(1LL, atoll(e));
-    return b;
-}
-
 static Src64 src_from(const Src64& s, long long b) {  // particles b.. of s
     Src64 r = s;
     if (s.u64) {
@@ -2482,18 +2356,17 @@ static Src64 src_from(const Src64& s, long long b) {  // particles b.. of s
     return r;
 }
 
-// The whole call: every window of the image (window_grid) and, inside it, particle
-// batches of < 2^31 particles, each batch split in two while its records reach 2^31.
-// Batches after the first accumulate; the ratio of a batched map is formed at the end.
+// The whole call: every window of the image (window_grid) and, inside it, the particle
+// batches of for_batches.  Batches after the first accumulate; the ratio of a batched map
+// is formed at the end.
 // rows [row_lo, row_hi) of the image only (asp_project2d_rows; default the whole image),
 // d0 / d1 pointing at row row_lo: windows of <= window_rows tile rows from row_lo on.
 int project2d_full(Workspace& ws, const Grid& full, const Src64& s, const float* du,
                    const float* dv, const float* dh, const float* da0, const float* da1,
                    long long n, int kid, int flags, float* d0, float* d1, hipStream_t st,
-                   int row_lo = 0, int row_hi = -1, const XArgs* xa = nullptr, int nxp = 0,
-                   float* const* xo = nullptr) {
+                   int device, int row_lo = 0, int row_hi = -1, const XArgs* xa = nullptr,
+                   int nxp = 0, float* const* xo = nullptr) {
     const int wr = window_rows(full);
-    const long long B = max_batch();
     long long agg[kNStats] = {0};
     if (row_hi < 0) row_hi = full.gnx;
     for (int r0 = row_lo; r0 < row_hi; r0 += wr * kTile) {
@@ -2503,61 +2376,53 @@ int project2d_full(Workspace& ws, const Grid& full, const Src64& s, const float*
         float* w1 = d1 ? d1 + off : nullptr;
         float* wx[4] = {nullptr, nullptr, nullptr, nullptr};  // the extra properties' maps
         for (int j = 0; j < nxp; ++j) wx[j] = xo[j] + off;
-        std::vector<std::pair<long long, long long>> todo;  // batches, last first
-        for (long long a = ((n - 1) / B) * B; a >= 0; a -= B)
-            todo.push_back({a, std::min(n, a + B)});
-        if (todo.empty()) todo.push_back({0, 0});
-        bool batched = todo.size() > 1;
         int passes = 0;
-        while (!todo.empty()) {
-            const auto [a, b] = todo.back();
-            todo.pop_back();
+        ASP_TRY(for_batches(n, [&](long long a, long long b, int i) -> int {
             int f = flags;
-            if (batched || b - a < n) f &= ~ASP_F_RATIO;  // ratio after the last batch
-            if (passes > 0) f |= ASP_F_ACCUMULATE;
+            if (b - a < n) f &= ~ASP_F_RATIO;  // ratio after the last batch
+            if (i > 0) f |= ASP_F_ACCUMULATE;
             XArgs xb{};
             if (xa) {
                 xb = *xa;
                 for (int j = 0; j < 4; ++j) xb.a[j] += a;
             }
-            const int rc = project2d_device(ws, g, src_from(s, a), du + a, dv + a, dh + a,
-                                            da0 + a, da1 ? da1 + a : nullptr, b - a, kid, f,
-                                            w0, w1, st, nullptr, xa ? &xb : nullptr, nxp, wx);
-            if (rc == kRetSplit) {
-                if (b - a < 2)
-                    return fail(ASP_ERR_UNSUPPORTED, "one particle makes >= 2^31 records");
-                const long long m = a + (b - a) / 2;
-                todo.push_back({m, b});
-                todo.push_back({a, m});
-                batched = true;
-                continue;
-            }
-            ASP_TRY(rc);
-            ++passes;
+            ASP_TRY(project2d_device(ws, g, src_from(s, a), du + a, dv + a, dh + a, da0 + a,
+                                     da1 ? da1 + a : nullptr, b - a, kid, f, w0, w1, st, nullptr,
+                                     xa ? &xb : nullptr, nxp, wx));
+            passes = i + 1;
             for (int k : {0, 1, 2, 6, 7, 8, 9, 10, 11, 12, 14}) agg[k] += ws.stats[k];
             agg[13] = std::max(agg[13], ws.stats[13]);
-        }
-        if (passes > 1 && (flags & ASP_F_RATIO)) {
-            const long long npix = (long long)g.nx * g.ny;
-            const long long blocks = std::min<long long>((npix + kBlock - 1) / kBlock, 8192);
-            StageMark m(ws, kSRatio, st);
-            hipLaunchKernelGGL(k_ratio, dim3((unsigned)std::max<long long>(1, blocks)), dim3(kBlock),
-                               0, st, w0, (const float*)w1, npix);
-            ASP_LAUNCHED();
-            m.done();
-        }
+            return ASP_OK;
+        }));
+        if (passes > 1 && (flags & ASP_F_RATIO))
+            ASP_TRY(launch_ratio(ws, w0, w1, (long long)g.nx * g.ny, st));
     }
     for (int k : {0, 1, 2, 6, 7, 8, 9, 10, 11, 12, 13, 14}) ws.stats[k] = agg[k];
     ws.stats[4] = (long long)((row_hi - row_lo + kTile - 1) / kTile) * full.nty;
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess && &ws != &g_ws[dev]) {  // asp_last_stats reads slot 0
-        // under slot 0's lock: a slot-0 call on another thread writes the same words (no
-        // cycle: slot-0 calls never take another slot's lock)
-        std::lock_guard<std::mutex> lk(g_ws[dev].mu);
-        std::copy(ws.stats, ws.stats + kNStats, g_ws[dev].stats);
-    }
+    stats_publish(ws, device);
     return ASP_OK;
 }
+
+// What a map entry point is asked for, apart from the particles: the image, the kernel,
+// the outputs and where to run.
+struct MapArgs {
+    double x_min, x_max, y_min, y_max;
+    int nx, ny, cs, kid, flags;
+    float *out0, *out1;
+    int device;
+    void* stream;
+    int row_lo = 0, row_hi = -1;     // asp_project2d_rows
+    float* const* xouts = nullptr;  // the maps of properties 2..
+};
+// The properties to deposit (T: the caller's precision): the first two, nxp further ones
+// (asp_project2d_props) and the SPH weights m (, rho) of asp_project2d_sph.
+template <class T>
+struct Props {
+    const T *a0 = nullptr, *a1 = nullptr;
+    const T* const* xprops = nullptr;
+    int nxp = 0;
+    const T *wm = nullptr, *wr = nullptr;
+};
 
 static int check_args(const void* a1, const float* out0, const float* out1, long long n, int kid,
                       int flags) {
@@ -2579,9 +2444,8 @@ static int check_args(const void* a1, const float* out0, const float* out1, long
     return ASP_OK;
 }
 
-static int setup_grid(double x_min, double x_max, double y_min, double y_max, int nx, int ny,
-                      int cs, Grid& g) {
-    if (!make_grid(x_min, x_max, y_min, y_max, nx, ny, cs, g))
+static int setup_grid(const MapArgs& m, Grid& g) {
+    if (!make_grid(m.x_min, m.x_max, m.y_min, m.y_max, m.nx, m.ny, m.cs, g))
         return fail(ASP_ERR_INVALID,
                     "invalid grid: need nx, ny, chunk_size >= 1, finite x_max > x_min, "
                     "y_max > y_min");
@@ -2646,93 +2510,110 @@ __global__ __launch_bounds__(kBlock) void k_weigh(const T* __restrict__ a, const
 }
 
 // The weighted fp32 copies of a0 (, a1) and properties 2.. into ws.wts (slot k = property
-// k), on st; the pointers are redirected to them.
+// k), on st; the pointers are redirected to them.  dev: m and rho are device arrays (else
+// they are staged into ws.inw first).
 template <class T>
-static int weigh_props(Workspace& ws, const T* a0, const T* a1, const T* const* xprops, int nxp,
-                       const T* m, const T* rho, long long n, hipStream_t st, const float** da0,
-                       const float** da1, const float** xw) {
+static int weigh_props(Workspace& ws, const Props<T>& p, const T* a0, const T* a1, long long n,
+                       bool dev, hipStream_t st, const float** da0, const float** da1,
+                       const float** xw) {
+    const T *dm = p.wm, *dr = p.wr;
+    if (!dev) {
+        const T* host[2] = {p.wm, p.wr};
+        for (int k = 0; k < 2; ++k) {
+            if (!host[k]) continue;
+            ASP_TRY(ensure(ws.inw[k], (size_t)n * sizeof(T)));
+            ASP_TRY(h2d_staged(ws, ws.inw[k].p, host[k], (size_t)n * sizeof(T), st));
+        }
+        dm = (const T*)ws.inw[0].p;
+        dr = p.wr ? (const T*)ws.inw[1].p : nullptr;
+    }
     const T* src[6] = {a0, a1, nullptr, nullptr, nullptr, nullptr};
-    for (int j = 0; j < nxp; ++j) src[2 + j] = xprops[j];
-    const long long blocks = std::min<long long>((n + kBlock - 1) / kBlock, 8192);
+    for (int j = 0; j < p.nxp; ++j) src[2 + j] = p.xprops[j];
     for (int k = 0; k < 6; ++k) {
         if (!src[k]) continue;
         ASP_TRY(ensure(ws.wts[k], (size_t)std::max(n, 1LL) * sizeof(float)));
         if (n > 0) {
-            hipLaunchKernelGGL(k_weigh<T>, dim3((unsigned)blocks), dim3(kBlock), 0, st, src[k], m,
-                               rho, (float*)ws.wts[k].p, n);
+            hipLaunchKernelGGL(k_weigh<T>, dim3(stream_blocks(n)), dim3(kBlock), 0, st, src[k], dm,
+                               dr, (float*)ws.wts[k].p, n);
             ASP_LAUNCHED();
         }
     }
     *da0 = (const float*)ws.wts[0].p;
     if (a1) *da1 = (const float*)ws.wts[1].p;
-    for (int j = 0; j < nxp; ++j) xw[j] = (const float*)ws.wts[2 + j].p;
+    for (int j = 0; j < p.nxp; ++j) xw[j] = (const float*)ws.wts[2 + j].p;
     return ASP_OK;
 }
 
-static int project2d(const float* u, const float* v, const float* h, const float* a0,
-                     const float* a1, long long n, double x_min, double x_max, double y_min,
-                     double y_max, int nx, int ny, int cs, int kid, int flags, float* out0,
-                     float* out1, int device, void* stream, int row_lo = 0, int row_hi = -1,
-                     const float* const* xprops = nullptr, int nxp = 0,
-                     float* const* xouts = nullptr, const float* wm = nullptr,
-                     const float* wr = nullptr) {
-    ASP_TRY(check_args(a1, out0, out1, n, kid, flags));
-    ASP_TRY(check_props(nxp, (const void* const*)xprops, xouts, flags));
-    if (nxp > 0 && !a1) return fail(ASP_ERR_INVALID, "properties 2.. need a1 / out1");
-    if (n > 0 && (!u || !v || !h || !a0)) return fail(ASP_ERR_INVALID, "NULL particle array");
-    Grid g;
-    ASP_TRY(setup_grid(x_min, x_max, y_min, y_max, nx, ny, cs, g));
-    if (row_hi < 0) row_hi = nx;
-    if (row_lo < 0 || row_lo >= row_hi || row_hi > nx)
-        return fail(ASP_ERR_INVALID, "rows: need 0 <= row_lo < row_hi <= nx");
-    nx = row_hi - row_lo;  // the rows this call writes (the grid keeps the whole image's)
-    ASP_TRY(set_device(device));
-    Workspace& ws = slot_ws(device, map_slot(device, (hipStream_t)stream));
+// What every map entry point checks first (arrays: the particle arrays are all given).
+template <class T>
+static int check_map(const MapArgs& m, const Props<T>& p, long long n, bool arrays) {
+    ASP_TRY(check_args(p.a1, m.out0, m.out1, n, m.kid, m.flags));
+    ASP_TRY(check_props(p.nxp, (const void* const*)p.xprops, m.xouts, m.flags));
+    if (p.nxp > 0 && !p.a1) return fail(ASP_ERR_INVALID, "properties 2.. need a1 / out1");
+    if (n > 0 && !arrays) return fail(ASP_ERR_INVALID, "NULL particle array");
+    return ASP_OK;
+}
+
+// The rest of a map call's prologue: the device, the workspace slot of the call's stream
+// under its lock, ordered behind the slot's previous call; body(ws, st) is the call.
+template <class F>
+static int with_workspace(const MapArgs& m, F&& body) {
+    ASP_TRY(set_device(m.device));
+    hipStream_t st = (hipStream_t)m.stream;
+    Workspace& ws = slot_ws(m.device, map_slot(m.device, st));
     std::lock_guard<std::mutex> lock(ws.mu);
-    hipStream_t st = (hipStream_t)stream;
     ASP_TRY(ws_begin(ws, st));
     WsEnd ws_end_(ws, st);
-    const int nout = out1 ? 2 : 1;
-    const bool dev = flags & ASP_F_DEVICE_PTRS;
-    const long long npix = (long long)nx * ny;
-    const float *du = u, *dv = v, *dh = h, *da0 = a0, *da1 = a1;
-    float *d0 = out0, *d1 = out1;
-    if (!dev) {
-        const float* src[5] = {u, v, h, a0, a1};
-        for (int k = 0; k < 4 + (nout == 2); ++k) {
-            ASP_TRY(ensure(ws.in[k], (size_t)n * sizeof(float)));
-            ASP_TRY(h2d_staged(ws, ws.in[k].p, src[k], (size_t)n * sizeof(float), st));
-        }
-        du = (const float*)ws.in[0].p;
-        dv = (const float*)ws.in[1].p;
-        dh = (const float*)ws.in[2].p;
-        da0 = (const float*)ws.in[3].p;
-        da1 = nout == 2 ? (const float*)ws.in[4].p : nullptr;
-        ASP_TRY(host_outputs(ws, out0, out1, npix, flags, st, d0, d1));
-    }
-    const float* xw[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int j = 0; j < nxp; ++j) xw[j] = xprops[j];
-    if (wm) {  // asp_project2d_sph: the properties times m / rho
-        const float *dm = wm, *dr = wr;
-        if (!dev) {
-            const float* src[2] = {wm, wr};
-            for (int k = 0; k < 2; ++k) {
-                if (!src[k]) continue;
-                ASP_TRY(ensure(ws.inw[k], (size_t)n * sizeof(float)));
-                ASP_TRY(h2d_staged(ws, ws.inw[k].p, src[k], (size_t)n * sizeof(float), st));
-            }
-            dm = (const float*)ws.inw[0].p;
-            dr = wr ? (const float*)ws.inw[1].p : nullptr;
-        }
-        ASP_TRY(weigh_props<float>(ws, da0, da1, xprops, nxp, dm, dr, n, st, &da0, &da1, xw));
-    }
-    const Src64 s{nullptr, nullptr, nullptr, nullptr, nullptr, 0, du, dv, dh};
-    XArgs xa{};
-    for (int j = 0; j < 4; ++j) xa.a[j] = j < nxp ? xw[j] : (nxp ? xw[0] : nullptr);
-    ASP_TRY(project2d_full(ws, g, s, du, dv, dh, da0, da1, n, kid, flags, d0, d1, st, row_lo,
-                           row_hi, nxp ? &xa : nullptr, nxp, xouts));
-    if (!dev) ASP_TRY(host_results(out0, out1, d0, d1, npix, st));
+    ASP_TRY(body(ws, st));
     return ws_end_.finish();
+}
+
+// xw: the fp32 arrays of properties 2.. (unused entries repeat the first)
+static XArgs extra_args(const float* const* xw, int nxp) {
+    XArgs xa{};
+    for (int j = 0; j < 4; ++j) xa.a[j] = nxp ? xw[j < nxp ? j : 0] : nullptr;
+    return xa;
+}
+
+static int project2d(const float* u, const float* v, const float* h, long long n,
+                     const Props<float>& p, const MapArgs& m) {
+    ASP_TRY(check_map(m, p, n, u && v && h && p.a0));
+    Grid g;
+    ASP_TRY(setup_grid(m, g));
+    const int row_lo = m.row_lo, row_hi = m.row_hi < 0 ? m.nx : m.row_hi;
+    if (row_lo < 0 || row_lo >= row_hi || row_hi > m.nx)
+        return fail(ASP_ERR_INVALID, "rows: need 0 <= row_lo < row_hi <= nx");
+    return with_workspace(m, [&](Workspace& ws, hipStream_t st) -> int {
+        const int nout = m.out1 ? 2 : 1;
+        const bool dev = m.flags & ASP_F_DEVICE_PTRS;
+        // the rows this call writes (the grid keeps the whole image's)
+        const long long npix = (long long)(row_hi - row_lo) * m.ny;
+        const float *du = u, *dv = v, *dh = h, *da0 = p.a0, *da1 = p.a1;
+        float *d0 = m.out0, *d1 = m.out1;
+        if (!dev) {
+            const float* src[5] = {u, v, h, p.a0, p.a1};
+            for (int k = 0; k < 4 + (nout == 2); ++k) {
+                ASP_TRY(ensure(ws.in[k], (size_t)n * sizeof(float)));
+                ASP_TRY(h2d_staged(ws, ws.in[k].p, src[k], (size_t)n * sizeof(float), st));
+            }
+            du = (const float*)ws.in[0].p;
+            dv = (const float*)ws.in[1].p;
+            dh = (const float*)ws.in[2].p;
+            da0 = (const float*)ws.in[3].p;
+            da1 = nout == 2 ? (const float*)ws.in[4].p : nullptr;
+            ASP_TRY(host_outputs(ws, m.out0, m.out1, npix, m.flags, st, d0, d1));
+        }
+        const float* xw[4] = {nullptr, nullptr, nullptr, nullptr};
+        for (int j = 0; j < p.nxp; ++j) xw[j] = p.xprops[j];
+        if (p.wm)  // asp_project2d_sph: the properties times m / rho
+            ASP_TRY(weigh_props<float>(ws, p, da0, da1, n, dev, st, &da0, &da1, xw));
+        const Src64 s{nullptr, nullptr, nullptr, nullptr, nullptr, 0, du, dv, dh};
+        const XArgs xa = extra_args(xw, p.nxp);
+        ASP_TRY(project2d_full(ws, g, s, du, dv, dh, da0, da1, n, m.kid, m.flags, d0, d1, st,
+                               m.device, row_lo, row_hi, p.nxp ? &xa : nullptr, p.nxp, m.xouts));
+        if (!dev) ASP_TRY(host_results(m.out0, m.out1, d0, d1, npix, st));
+        return ASP_OK;
+    });
 }
 
 // create_image on the reader's fp64 arrays: stage (axis selection, fp32 working copies in
@@ -2744,95 +2625,84 @@ __global__ __launch_bounds__(kBlock) void k_to_f32(const double* __restrict__ a,
         b[i] = (float)a[i];  // round to nearest, as NumPy's astype(float32)
 }
 
-static int project2d_f64(const double* pos, const double* h, const double* a0,
-                         const double* a1, long long n, int axis, double x_min, double x_max,
-                         double y_min, double y_max, int nx, int ny, int cs, int kid, int flags,
-                         float* out0, float* out1, int device, void* stream,
-                         const double* const* xprops = nullptr, int nxp = 0,
-                         float* const* xouts = nullptr, const double* wm = nullptr,
-                         const double* wr = nullptr) {
-    ASP_TRY(check_args(a1, out0, out1, n, kid, flags));
-    ASP_TRY(check_props(nxp, (const void* const*)xprops, xouts, flags));
-    if (nxp > 0 && !a1) return fail(ASP_ERR_INVALID, "properties 2.. need a1 / out1");
-    if (n > 0 && (!pos || !h || !a0)) return fail(ASP_ERR_INVALID, "NULL particle array");
-    // axis: the pixel test's axis, | ASP_AXIS_CULL(c) to cull on axis c's columns
-    const int cull_axis = (axis >> 4) ? (axis >> 4) - 1 : (axis & 15);
+// axis: the pixel test's axis, | ASP_AXIS_CULL(c) to cull on axis c's columns
+static int decode_axis(int& axis, int& cull_axis) {
+    cull_axis = (axis >> 4) ? (axis >> 4) - 1 : (axis & 15);
     axis &= 15;
     if (axis < 0 || axis > 2 || cull_axis < 0 || cull_axis > 2)
         return fail(ASP_ERR_INVALID, "projection axis must be 0 (X), 1 (Y) or 2 (Z)");
-    Grid g;
-    ASP_TRY(setup_grid(x_min, x_max, y_min, y_max, nx, ny, cs, g));
-    g.mixed = cull_axis != axis;
-    ASP_TRY(set_device(device));
-    Workspace& ws = slot_ws(device, map_slot(device, (hipStream_t)stream));
-    std::lock_guard<std::mutex> lock(ws.mu);
-    hipStream_t st = (hipStream_t)stream;
-    ASP_TRY(ws_begin(ws, st));
-    WsEnd ws_end_(ws, st);
-    const int nout = out1 ? 2 : 1;
-    const bool dev = flags & ASP_F_DEVICE_PTRS;
-    const bool dev_out = dev || (flags & ASP_F_DEVICE_OUTPUTS);  // maps stay on the device
-    const long long npix = (long long)nx * ny;
-    const double *dpos = pos, *dh64 = h, *da0 = a0, *da1 = a1;
-    float *d0 = out0, *d1 = out1;
-    if (!dev) {
-        // the fp64 arrays stay resident: the exact re-decisions read positions and h
-        const double* src[4] = {pos, h, a0, a1};
-        const size_t words[4] = {3, 1, 1, 1};
-        for (int k = 0; k < 3 + (nout == 2); ++k) {
-            ASP_TRY(ensure(ws.in64[k], (size_t)n * words[k] * sizeof(double)));
-            ASP_TRY(h2d_staged(ws, ws.in64[k].p, src[k], (size_t)n * words[k] * sizeof(double), st));
-        }
-        dpos = (const double*)ws.in64[0].p;
-        dh64 = (const double*)ws.in64[1].p;
-        da0 = (const double*)ws.in64[2].p;
-        da1 = nout == 2 ? (const double*)ws.in64[3].p : nullptr;
-        if (!dev_out) ASP_TRY(host_outputs(ws, out0, out1, npix, flags, st, d0, d1));
-    }
-    for (int k = 0; k < 4 + (nout == 2); ++k) ASP_TRY(ensure(ws.in[k], (size_t)n * sizeof(float)));
-    float* f[5] = {(float*)ws.in[0].p, (float*)ws.in[1].p, (float*)ws.in[2].p, (float*)ws.in[3].p,
-                   nout == 2 ? (float*)ws.in[4].p : nullptr};
-    // asp_project2d_sph_f64: the properties' fp32 copies are m / rho * A (weigh_props), so
-    // the staging converts positions and h only
-    ASP_TRY(stage_device(dpos, dh64, wm ? nullptr : da0, wm ? nullptr : da1, n, axis, f[0], f[1],
-                         f[2], wm ? nullptr : f[3], wm ? nullptr : f[4], st));
-    const float* fa0 = f[3];
-    const float* fa1 = f[4];
-    const float* xw[4] = {nullptr, nullptr, nullptr, nullptr};
-    if (wm) {
-        const double *dm = wm, *dr = wr;
-        if (!dev) {
-            const double* src[2] = {wm, wr};
-            for (int k = 0; k < 2; ++k) {
-                if (!src[k]) continue;
-                ASP_TRY(ensure(ws.inw[k], (size_t)n * sizeof(double)));
-                ASP_TRY(h2d_staged(ws, ws.inw[k].p, src[k], (size_t)n * sizeof(double), st));
-            }
-            dm = (const double*)ws.inw[0].p;
-            dr = wr ? (const double*)ws.inw[1].p : nullptr;
-        }
-        ASP_TRY(weigh_props<double>(ws, da0, da1, xprops, nxp, dm, dr, n, st, &fa0, &fa1, xw));
-    }
+    return ASP_OK;
+}
+
+// The resident fp64 (n, 3) positions and h as the exact source of the image-plane
+// coordinates, beside their fp32 working copies f = {u, v, h}.
+static Src64 src64_from_positions(const double* dpos, const double* dh, int axis, int cull_axis,
+                                  float* const* f) {
     static const int cols[3][2] = {{1, 2}, {0, 2}, {0, 1}};  // _projector.py:38-46
-    const Src64 s{dpos + cols[axis][0], dpos + cols[axis][1], dpos + cols[cull_axis][0],
-                  dpos + cols[cull_axis][1], dh64, 3, f[0], f[1], f[2]};
-    XArgs xa{};
-    for (int j = 0; j < nxp && !wm; ++j) {  // fp32 working copies of properties 2..
-        ASP_TRY(ensure(ws.inx[j], (size_t)std::max(n, 1LL) * sizeof(float)));
-        if (n > 0) {
-            const long long blocks = std::min<long long>((n + kBlock - 1) / kBlock, 8192);
-            hipLaunchKernelGGL(k_to_f32, dim3((unsigned)blocks), dim3(kBlock), 0, st, xprops[j],
-                               (float*)ws.inx[j].p, n);
-            ASP_LAUNCHED();
+    return Src64{dpos + cols[axis][0], dpos + cols[axis][1], dpos + cols[cull_axis][0],
+                 dpos + cols[cull_axis][1], dh, 3, f[0], f[1], f[2]};
+}
+
+static int project2d_f64(const double* pos, const double* h, long long n, int axis,
+                         const Props<double>& p, const MapArgs& m) {
+    ASP_TRY(check_map(m, p, n, pos && h && p.a0));
+    int cull_axis = 0;
+    ASP_TRY(decode_axis(axis, cull_axis));
+    Grid g;
+    ASP_TRY(setup_grid(m, g));
+    g.mixed = cull_axis != axis;
+    return with_workspace(m, [&](Workspace& ws, hipStream_t st) -> int {
+        const int nout = m.out1 ? 2 : 1;
+        const bool dev = m.flags & ASP_F_DEVICE_PTRS;
+        const bool dev_out = dev || (m.flags & ASP_F_DEVICE_OUTPUTS);  // maps stay on the device
+        const long long npix = (long long)m.nx * m.ny;
+        const double *dpos = pos, *dh64 = h, *da0 = p.a0, *da1 = p.a1;
+        float *d0 = m.out0, *d1 = m.out1;
+        if (!dev) {
+            // the fp64 arrays stay resident: the exact re-decisions read positions and h
+            const double* src[4] = {pos, h, p.a0, p.a1};
+            const size_t words[4] = {3, 1, 1, 1};
+            for (int k = 0; k < 3 + (nout == 2); ++k) {
+                const size_t bytes = (size_t)n * words[k] * sizeof(double);
+                ASP_TRY(ensure(ws.in64[k], bytes));
+                ASP_TRY(h2d_staged(ws, ws.in64[k].p, src[k], bytes, st));
+            }
+            dpos = (const double*)ws.in64[0].p;
+            dh64 = (const double*)ws.in64[1].p;
+            da0 = (const double*)ws.in64[2].p;
+            da1 = nout == 2 ? (const double*)ws.in64[3].p : nullptr;
+            if (!dev_out) ASP_TRY(host_outputs(ws, m.out0, m.out1, npix, m.flags, st, d0, d1));
         }
-        xw[j] = (const float*)ws.inx[j].p;
-    }
-    for (int j = 0; j < 4; ++j) xa.a[j] = nxp ? xw[j < nxp ? j : 0] : nullptr;
-    ASP_TRY(project2d_full(ws, g, s, f[0], f[1], f[2], fa0, fa1, n, kid,
-                           (flags & ~ASP_F_DEVICE_OUTPUTS) | ASP_F_DEVICE_PTRS, d0, d1, st, 0, -1,
-                           nxp ? &xa : nullptr, nxp, xouts));
-    if (!dev_out) ASP_TRY(host_results(out0, out1, d0, d1, npix, st));
-    return ws_end_.finish();
+        for (int k = 0; k < 4 + (nout == 2); ++k)
+            ASP_TRY(ensure(ws.in[k], (size_t)n * sizeof(float)));
+        float* f[5] = {(float*)ws.in[0].p, (float*)ws.in[1].p, (float*)ws.in[2].p,
+                       (float*)ws.in[3].p, nout == 2 ? (float*)ws.in[4].p : nullptr};
+        // asp_project2d_sph_f64: the properties' fp32 copies are m / rho * A (weigh_props), so
+        // the staging converts positions and h only
+        const bool sph = p.wm != nullptr;
+        ASP_TRY(stage_device(dpos, dh64, sph ? nullptr : da0, sph ? nullptr : da1, n, axis, f[0],
+                             f[1], f[2], sph ? nullptr : f[3], sph ? nullptr : f[4], st));
+        const float* fa0 = f[3];
+        const float* fa1 = f[4];
+        const float* xw[4] = {nullptr, nullptr, nullptr, nullptr};
+        if (sph) ASP_TRY(weigh_props<double>(ws, p, da0, da1, n, dev, st, &fa0, &fa1, xw));
+        const Src64 s = src64_from_positions(dpos, dh64, axis, cull_axis, f);
+        for (int j = 0; j < p.nxp && !sph; ++j) {  // fp32 working copies of properties 2..
+            ASP_TRY(ensure(ws.inx[j], (size_t)std::max(n, 1LL) * sizeof(float)));
+            if (n > 0) {
+                hipLaunchKernelGGL(k_to_f32, dim3(stream_blocks(n)), dim3(kBlock), 0, st,
+                                   p.xprops[j], (float*)ws.inx[j].p, n);
+                ASP_LAUNCHED();
+            }
+            xw[j] = (const float*)ws.inx[j].p;
+        }
+        const XArgs xa = extra_args(xw, p.nxp);
+        ASP_TRY(project2d_full(ws, g, s, f[0], f[1], f[2], fa0, fa1, n, m.kid,
+                               (m.flags & ~ASP_F_DEVICE_OUTPUTS) | ASP_F_DEVICE_PTRS, d0, d1, st,
+                               m.device, 0, -1, p.nxp ? &xa : nullptr, p.nxp, m.xouts));
+        if (!dev_out) ASP_TRY(host_results(m.out0, m.out1, d0, d1, npix, st));
+        return ASP_OK;
+    });
 }
 
 // The kernel_func plug-in session (asp_pairs_begin / _emit / _end): the particles are
@@ -2894,22 +2764,19 @@ static int pairs_bin(PairsSession& S, int tx0) {
     return ASP_OK;
 }
 
-static int pairs_begin(const double* pos, const double* h, long long n, int axis, double x_min,
-                       double x_max, double y_min, double y_max, int nx, int ny, int cs,
-                       int flags, int device, void* stream, long long* tile_pairs,
-                       PairsSession** out) {
+static int pairs_begin(const double* pos, const double* h, long long n, int axis,
+                       const MapArgs& m, long long* tile_pairs, PairsSession** out) {
+    const int flags = m.flags, device = m.device;
     *out = nullptr;
     if (n < 0) return fail(ASP_ERR_INVALID, "n < 0");
     if (n > 0x7fffffffLL)
         return fail(ASP_ERR_UNSUPPORTED, "kernel_func plug-in: n >= 2^31 particles per call");
     if (n > 0 && (!pos || !h)) return fail(ASP_ERR_INVALID, "NULL particle array");
     if (!tile_pairs) return fail(ASP_ERR_INVALID, "NULL tile_pairs");
-    const int cull_axis = (axis >> 4) ? (axis >> 4) - 1 : (axis & 15);
-    axis &= 15;
-    if (axis < 0 || axis > 2 || cull_axis < 0 || cull_axis > 2)
-        return fail(ASP_ERR_INVALID, "projection axis must be 0 (X), 1 (Y) or 2 (Z)");
+    int cull_axis = 0;
+    ASP_TRY(decode_axis(axis, cull_axis));
     Grid g;
-    ASP_TRY(setup_grid(x_min, x_max, y_min, y_max, nx, ny, cs, g));
+    ASP_TRY(setup_grid(m, g));
     g.mixed = cull_axis != axis;
     ASP_TRY(set_device(device));
     PairsSession* S = new (std::nothrow) PairsSession();
@@ -2918,7 +2785,7 @@ static int pairs_begin(const double* pos, const double* h, long long n, int axis
     S->n = n;
     S->device = device;
     S->flags = flags;
-    S->st = (hipStream_t)stream;
+    S->st = (hipStream_t)m.stream;
     Workspace& ws = S->ws;
     auto bail = [&](int rc) {
         (void)hipStreamSynchronize(S->st);
@@ -2947,9 +2814,7 @@ static int pairs_begin(const double* pos, const double* h, long long n, int axis
                                     nullptr, nullptr, S->st);
         if (rc != ASP_OK) return bail(rc);
     }
-    static const int cols[3][2] = {{1, 2}, {0, 2}, {0, 1}};  // _projector.py:38-46
-    S->s = Src64{dpos + cols[axis][0], dpos + cols[axis][1], dpos + cols[cull_axis][0],
-                 dpos + cols[cull_axis][1], dh64, 3, f[0], f[1], f[2]};
+    S->s = src64_from_positions(dpos, dh64, axis, cull_axis, f);
     for (int k = 0; k < 3; ++k) S->f[k] = f[k];
     // every window once: its per-tile pair totals (the last window stays binned)
     S->tile_pairs.assign((size_t)g.ntiles, 0);
@@ -3058,6 +2923,23 @@ static int pairs_end(PairsSession* S) {
     return ASP_OK;
 }
 
+// The first two of the props / outs lists are a0 / a1 and out0 / out1, the rest properties
+// 2..5 (asp_project2d_props, asp_project2d_sph and their fp64 forms).
+template <class T>
+static int slice_props(const T* const* props, float* const* outs, int nprops, Props<T>& p,
+                       MapArgs& m) {
+    if (nprops < 1 || nprops > 6 || !props || !outs)
+        return fail(ASP_ERR_INVALID, "nprops must be 1 .. 6 with props / outs given");
+    p.a0 = props[0];
+    p.a1 = nprops > 1 ? props[1] : nullptr;
+    p.xprops = nprops > 2 ? props + 2 : nullptr;
+    p.nxp = std::max(0, nprops - 2);
+    m.out0 = outs[0];
+    m.out1 = nprops > 1 ? outs[1] : nullptr;
+    m.xouts = nprops > 2 ? outs + 2 : nullptr;
+    return ASP_OK;
+}
+
 }  // namespace asp
 
 // ==================================================================================
@@ -3082,8 +2964,9 @@ int asp_project2d(const float* u, const float* v, const float* h, const float* a
                   double v_max, int32_t nx, int32_t ny, int32_t chunk_size, int32_t kernel_id,
                   int32_t flags, float* out0, float* out1, int32_t device, void* stream) {
     t_err.clear();
-    return project2d(u, v, h, a0, a1, n, u_min, u_max, v_min, v_max, nx, ny, chunk_size,
-                     kernel_id, flags, out0, out1, device, stream);
+    return project2d(u, v, h, n, Props<float>{a0, a1},
+                     MapArgs{u_min, u_max, v_min, v_max, nx, ny, chunk_size, kernel_id, flags, out0,
+                             out1, device, stream});
 }
 
 int asp_project2d_rows(const float* u, const float* v, const float* h, const float* a0,
@@ -3092,8 +2975,9 @@ int asp_project2d_rows(const float* u, const float* v, const float* h, const flo
                        int32_t row_hi, int32_t kernel_id, int32_t flags, float* out0,
                        float* out1, int32_t device, void* stream) {
     t_err.clear();
-    return project2d(u, v, h, a0, a1, n, u_min, u_max, v_min, v_max, nx, ny, chunk_size,
-                     kernel_id, flags, out0, out1, device, stream, row_lo, row_hi);
+    return project2d(u, v, h, n, Props<float>{a0, a1},
+                     MapArgs{u_min, u_max, v_min, v_max, nx, ny, chunk_size, kernel_id, flags, out0,
+                             out1, device, stream, row_lo, row_hi});
 }
 
 int asp_project2d_props(const float* u, const float* v, const float* h, const float* const* props,
@@ -3102,13 +2986,11 @@ int asp_project2d_props(const float* u, const float* v, const float* h, const fl
                         int32_t kernel_id, int32_t flags, float* const* outs, int32_t device,
                         void* stream) {
     t_err.clear();
-    if (nprops < 1 || nprops > 6 || !props || !outs)
-        return fail(ASP_ERR_INVALID, "nprops must be 1 .. 6 with props / outs given");
-    return project2d(u, v, h, props[0], nprops > 1 ? props[1] : nullptr, n, u_min, u_max, v_min,
-                     v_max, nx, ny, chunk_size, kernel_id, flags, outs[0],
-                     nprops > 1 ? outs[1] : nullptr, device, stream, 0, -1,
-                     nprops > 2 ? props + 2 : nullptr, std::max(0, nprops - 2),
-                     nprops > 2 ? outs + 2 : nullptr);
+    Props<float> p;
+    MapArgs m{u_min, u_max, v_min, v_max, nx, ny, chunk_size, kernel_id, flags, nullptr,
+              nullptr, device, stream};
+    ASP_TRY(slice_props(props, outs, nprops, p, m));
+    return project2d(u, v, h, n, p, m);
 }
 
 int asp_project2d_props_f64(const double* positions, const double* h,
@@ -3117,13 +2999,11 @@ int asp_project2d_props_f64(const double* positions, const double* h,
                             int32_t ny, int32_t chunk_size, int32_t kernel_id, int32_t flags,
                             float* const* outs, int32_t device, void* stream) {
     t_err.clear();
-    if (nprops < 1 || nprops > 6 || !props || !outs)
-        return fail(ASP_ERR_INVALID, "nprops must be 1 .. 6 with props / outs given");
-    return project2d_f64(positions, h, props[0], nprops > 1 ? props[1] : nullptr, n, axis, u_min,
-                         u_max, v_min, v_max, nx, ny, chunk_size, kernel_id, flags, outs[0],
-                         nprops > 1 ? outs[1] : nullptr, device, stream,
-                         nprops > 2 ? props + 2 : nullptr, std::max(0, nprops - 2),
-                         nprops > 2 ? outs + 2 : nullptr);
+    Props<double> p;
+    MapArgs m{u_min, u_max, v_min, v_max, nx, ny, chunk_size, kernel_id, flags, nullptr,
+              nullptr, device, stream};
+    ASP_TRY(slice_props(props, outs, nprops, p, m));
+    return project2d_f64(positions, h, n, axis, p, m);
 }
 
 int asp_project2d_sph(const float* u, const float* v, const float* h, const float* mass,
@@ -3132,14 +3012,14 @@ int asp_project2d_sph(const float* u, const float* v, const float* h, const floa
                       int32_t ny, int32_t chunk_size, int32_t kernel_id, int32_t flags,
                       float* const* outs, int32_t device, void* stream) {
     t_err.clear();
-    if (nprops < 1 || nprops > 6 || !props || !outs)
-        return fail(ASP_ERR_INVALID, "nprops must be 1 .. 6 with props / outs given");
+    Props<float> p;
+    MapArgs m{u_min, u_max, v_min, v_max, nx, ny, chunk_size, kernel_id, flags, nullptr,
+              nullptr, device, stream};
+    ASP_TRY(slice_props(props, outs, nprops, p, m));
     if (n > 0 && !mass) return fail(ASP_ERR_INVALID, "NULL mass array");
-    return project2d(u, v, h, props[0], nprops > 1 ? props[1] : nullptr, n, u_min, u_max, v_min,
-                     v_max, nx, ny, chunk_size, kernel_id, flags, outs[0],
-                     nprops > 1 ? outs[1] : nullptr, device, stream, 0, -1,
-                     nprops > 2 ? props + 2 : nullptr, std::max(0, nprops - 2),
-                     nprops > 2 ? outs + 2 : nullptr, mass, rho);
+    p.wm = mass;
+    p.wr = rho;
+    return project2d(u, v, h, n, p, m);
 }
 
 int asp_project2d_sph_f64(const double* positions, const double* h, const double* mass,
@@ -3149,14 +3029,14 @@ int asp_project2d_sph_f64(const double* positions, const double* h, const double
                           int32_t kernel_id, int32_t flags, float* const* outs, int32_t device,
                           void* stream) {
     t_err.clear();
-    if (nprops < 1 || nprops > 6 || !props || !outs)
-        return fail(ASP_ERR_INVALID, "nprops must be 1 .. 6 with props / outs given");
+    Props<double> p;
+    MapArgs m{u_min, u_max, v_min, v_max, nx, ny, chunk_size, kernel_id, flags, nullptr,
+              nullptr, device, stream};
+    ASP_TRY(slice_props(props, outs, nprops, p, m));
     if (n > 0 && !mass) return fail(ASP_ERR_INVALID, "NULL mass array");
-    return project2d_f64(positions, h, props[0], nprops > 1 ? props[1] : nullptr, n, axis, u_min,
-                         u_max, v_min, v_max, nx, ny, chunk_size, kernel_id, flags, outs[0],
-                         nprops > 1 ? outs[1] : nullptr, device, stream,
-                         nprops > 2 ? props + 2 : nullptr, std::max(0, nprops - 2),
-                         nprops > 2 ? outs + 2 : nullptr, mass, rho);
+    p.wm = mass;
+    p.wr = rho;
+    return project2d_f64(positions, h, n, axis, p, m);
 }
 
 int asp_project2d_f64(const double* positions, const double* h, const double* a0,
@@ -3165,8 +3045,9 @@ int asp_project2d_f64(const double* positions, const double* h, const double* a0
                       int32_t kernel_id, int32_t flags, float* out0, float* out1, int32_t device,
                       void* stream) {
     t_err.clear();
-    return project2d_f64(positions, h, a0, a1, n, axis, u_min, u_max, v_min, v_max, nx, ny,
-                         chunk_size, kernel_id, flags, out0, out1, device, stream);
+    return project2d_f64(positions, h, n, axis, Props<double>{a0, a1},
+                         MapArgs{u_min, u_max, v_min, v_max, nx, ny, chunk_size, kernel_id, flags,
+                                 out0, out1, device, stream});
 }
 
 int asp_pairs_begin(const double* positions, const double* h, int64_t n, int32_t axis,
@@ -3176,8 +3057,10 @@ int asp_pairs_begin(const double* positions, const double* h, int64_t n, int32_t
     t_err.clear();
     if (!session) return fail(ASP_ERR_INVALID, "NULL session");
     PairsSession* S = nullptr;
-    const int rc = pairs_begin(positions, h, n, axis, u_min, u_max, v_min, v_max, nx, ny,
-                               chunk_size, flags, device, stream, (long long*)tile_pairs, &S);
+    const int rc = pairs_begin(positions, h, n, axis,
+                               MapArgs{u_min, u_max, v_min, v_max, nx, ny, chunk_size,
+                                       ASP_KERNEL_INDICATOR, flags, nullptr, nullptr, device, stream},
+                               (long long*)tile_pairs, &S);
     *session = S;
     return rc;
 }
@@ -3347,8 +3230,7 @@ int asp_ratio(float* out0, const float* out1, int64_t n, int32_t device, void* s
     if (n < 0 || !out0 || !out1) return fail(ASP_ERR_INVALID, "bad argument");
     if (n == 0) return ASP_OK;
     ASP_TRY(set_device(device));
-    long long blocks = std::min<long long>((n + kBlock - 1) / kBlock, 8192);
-    hipLaunchKernelGGL(k_ratio, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(k_ratio, dim3(stream_blocks(n)), dim3(kBlock), 0, (hipStream_t)stream,
                        out0, out1, (long long)n);
     ASP_HIP(hipGetLastError());
     return ASP_OK;

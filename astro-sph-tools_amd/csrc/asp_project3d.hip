@@ -947,19 +947,16 @@ static bool make_grid3(const double* ext, int nx, int ny, int nz, int k_lo, int 
     // more bricks than one pass holds: windows of whole brick columns in x (window3); -1:
     // not even one brick column fits
     g.nb = (long long)g.nby * g.nbz > kMaxBricks ? -1 : (int)std::min<long long>(nb, 0x7fffffff);
-    g.lane_cols = kLaneCols;
-    if (const char* e = getenv("ASP_CUBE_LANE_COLS")) g.lane_cols = std::max(0, atoi(e));
-    g.diag = getenv("ASP_CUBE_DIAG") ? atoi(getenv("ASP_CUBE_DIAG")) : 0;
+    g.lane_cols = (int)env_int("ASP_CUBE_LANE_COLS", kLaneCols, 0);
+    g.diag = (int)env_int("ASP_CUBE_DIAG", 0);
     return true;
 }
 
-// internal: >= 2^31 records in one pass.  The speculative scatter (enqueued before the
-// counters are read) may already have written records into the spare capacity of the
-// existing buffer; the caller's split discards them.
-constexpr int kRetSplit3 = 1;
-
 // One window (w.i_lo, w.nxl; <= kMaxBricks bricks) of the cube on stream st: count,
 // scans, scatter (placement trials on a fresh record buffer), deposit, merge.
+// Returns kRetSplit when the pass would make >= 2^31 records.  The speculative scatter
+// (enqueued before the counters are read) may already have written records into the spare
+// capacity of the existing buffer; the caller's split discards them.
 static int cube_pass(Workspace& ws, const Grid3& g, const float* dx, const float* dy,
                      const float* dz, const float* dh, const float* da, long long n, int kid,
                      int acc, float* dout, hipStream_t st, long long* agg) {
@@ -970,10 +967,10 @@ static int cube_pass(Workspace& ws, const Grid3& g, const float* dx, const float
     // at 10^8: 512 / 384 / 256 / 128 -> cube 13.92-13.96 / 13.86-13.87 / 14.46-14.48 / 17.9 ms:
     // fewer scatter workgroups keep fewer (workgroup, brick) runs open, scatter 3.61 -> 3.44,
     // count 0.41 -> 0.54); ASP_CUBE_BLOCKS overrides (read per call)
-    const long long max_blk = getenv("ASP_CUBE_BLOCKS") ? std::max(2, atoi(getenv("ASP_CUBE_BLOCKS"))) : 384;
+    const long long max_blk = env_int("ASP_CUBE_BLOCKS", 384, 2);
     long long nblk = std::min<long long>(max_blk, std::max<long long>(1, (n + 8191) / 8192));
     // batch-interleaved count / scatter (ASP_CUBE_INTERLEAVE=0: contiguous ranges per block)
-    static const int inter = getenv("ASP_CUBE_INTERLEAVE") ? atoi(getenv("ASP_CUBE_INTERLEAVE")) : 1;
+    static const int inter = (int)env_int("ASP_CUBE_INTERLEAVE", 1);  // (read once per process)
     long long per_block = (n + nblk - 1) / nblk;
     nblk = (n + per_block - 1) / per_block;
     ASP_TRY(ensure(ws.hist, (size_t)nblk * g.nb * sizeof(int)));
@@ -982,17 +979,14 @@ static int cube_pass(Workspace& ws, const Grid3& g, const float* dx, const float
     // target item count: 1024 (round 5; 512 / 1024 / 2048 / 4096: deposit + merge 10.45 /
     // 9.99-10.04 / 10.06 / 10.15 ms, same process -- fewer split bricks, fewer fp64 slabs
     // to write and merge); ASP_CUBE_ITEMS overrides (read per call)
-    int target = 1024;
-    if (const char* e = getenv("ASP_CUBE_ITEMS")) target = std::max(64, atoi(e));
+    const int target = (int)env_int("ASP_CUBE_ITEMS", 1024, 64);
     ASP_TRY(ensure(ws.items, (size_t)(g.nb + target + 16) * sizeof(Item)));
     ASP_TRY(ensure(ws.iorder, (size_t)(g.nb + target + 16) * sizeof(int)));
-    const bool morton_order = getenv("ASP_CUBE_ITEM_ORDER") && atoi(getenv("ASP_CUBE_ITEM_ORDER")) == 0;  // A/B
+    const bool morton_order = env_int("ASP_CUBE_ITEM_ORDER", 1) == 0;  // A/B
     int* iord = morton_order ? nullptr : (int*)ws.iorder.p;
     ASP_TRY(ensure(ws.merges, (size_t)(g.nb + 16) * sizeof(Merge)));
-    ASP_TRY(ensure(ws.counters, cNum * sizeof(int)));
-    if (!ws.h_counters) ASP_HIP(hipHostMalloc((void**)&ws.h_counters, kMarks * cNum * sizeof(int)));
+    ASP_TRY(counters_begin(ws, cNum, st));
     int* dc = (int*)ws.counters.p;
-    ASP_HIP(hipMemsetAsync(dc, 0, cNum * sizeof(int), st));
     const size_t lds_bins = (size_t)g.nb * sizeof(int);
     {
         StageMark m(ws, kS3Count, st);
@@ -1027,8 +1021,7 @@ static int cube_pass(Workspace& ws, const Grid3& g, const float* dx, const float
         StageMark m(ws, kS3Scatter, st);
         // grouped workgroups (GRP 2) need an even count grid; ASP_CUBE_SGRP=1: one count
         // workgroup per scatter workgroup (A/B switch, read per call)
-        const char* ge = getenv("ASP_CUBE_SGRP");
-        const bool g2 = (ge ? atoi(ge) != 1 : true) && nblk % 2 == 0;
+        const bool g2 = env_int("ASP_CUBE_SGRP", 2) != 1 && nblk % 2 == 0;
         auto kern = g2 ? (probe ? k3_scatter<1, 2 * k3Block> : k3_scatter<0, 2 * k3Block>)
                        : (probe ? k3_scatter<1, k3Block> : k3_scatter<0, k3Block>);
         const int tb = g2 ? 2 * k3Block : k3Block;
@@ -1045,42 +1038,39 @@ static int cube_pass(Workspace& ws, const Grid3& g, const float* dx, const float
         m.done();
         return ASP_OK;
     };
-    auto scatter = [&](bool probe) { return scatter_launch(probe, 0x7ffffffeLL); };
     // One small read-back sizes the buffers.  With a record buffer left by an earlier call,
     // the scatter is enqueued BEFORE the host waits for the counters (it checks them against
     // that buffer's capacity itself), so the GPU does not idle across the host round trip
     // (as the 2-D path, asp_project2d.hip).
+    // The copy is on st itself (the 2-D map's is on the side stream, behind the second part
+    // of its tile scan there).
     ASP_TRY(ensure_side(ws));  // (its events)
     ASP_HIP(hipMemcpyAsync(ws.h_counters, dc, cNum * sizeof(int), hipMemcpyDeviceToHost, st));
     ASP_HIP(hipEventRecord(ws.cnt_ev, st));
-    const long long rec_cap =
-        (long long)std::min<size_t>(ws.recs.cap / (2 * sizeof(float4)), 0x7ffffffe);
-    const bool spec = ws.recs.p != nullptr && getenv("ASP_NO_SPECULATE") == nullptr;
+    const long long rec_cap = record_capacity(ws);
+    const bool spec = ws.recs.p != nullptr && speculate_on();
     if (spec) ASP_TRY(scatter_launch(false, rec_cap));
     ASP_HIP(hipEventSynchronize(ws.cnt_ev));
     n_items = ws.h_counters[cItems];
     n_recs = ws.h_counters[cRecs];
     n_slabs = ws.h_counters[cSlabs];
     n_merges = ws.h_counters[cMerges];
-    long long rec_limit = 0x7fffffffLL;  // 32-bit record cursors (ASP_MAX_RECORDS: tests)
-    if (const char* e = getenv("ASP_MAX_RECORDS")) rec_limit = std::max(1LL, atoll(e));
-    if (n_recs >= rec_limit) {  // the caller splits (a speculative scatter wrote into spare room)
-        if (spec) ASP_HIP(hipStreamSynchronize(st));
-        return kRetSplit3;
-    }
-    const bool pre = spec && n_recs <= rec_cap;  // the speculative scatter did the work
-    if (spec && !pre) ASP_HIP(hipStreamSynchronize(st));  // its no-op is done: buffer free
-    const void* recs_before = ws.recs.p;
-    ASP_TRY(ensure(ws.recs, (size_t)n_recs * 2 * sizeof(float4)));
+    bool pre = false;  // the speculative scatter did the work
+    ASP_TRY(settle_speculation(spec, n_recs, n_recs <= rec_cap, st, pre));
+    bool fresh = false;
+    ASP_TRY(ensure_records(ws, n_recs, fresh));
     ASP_TRY(ensure(ws.slabs, (size_t)n_slabs * kBrickVox * sizeof(double)));
-    bool placed = pre;  // a fresh record buffer: placement trials (asp_host.hpp)
-    if (!pre && ws.recs.p != recs_before)
-        ASP_TRY(place_records(ws, (size_t)n_recs * 2 * sizeof(float4), st,
-                              [&]() { return scatter(true); }, placed));
-    if (!placed) ASP_TRY(scatter(false));
+    bool placed = false;  // a fresh record buffer: placement trials (asp_host.hpp)
+    if (!pre && fresh)
+        ASP_TRY(place_records(ws, record_bytes(n_recs), st,
+                              [&]() { return scatter_launch(true, kNoRecordCap); }, placed));
+    if (!pre && !placed) ASP_TRY(scatter_launch(false, kNoRecordCap));
     {
         StageMark m(ws, kS3Deposit, st);
         size_t lds = (size_t)kBrickLds * sizeof(double) + (kBX + kBY + kBZ) * sizeof(double);
+        // (a plain pointer chain, not dispatch_kid: the cube has the one template parameter,
+        // and naming the kernels here keeps the order they are emitted in, on which the
+        // compiler's address arithmetic in k3_deposit<0> turned out to depend)
         auto kern = kid == 0 ? k3_deposit<0> : kid == 1 ? k3_deposit<1> : k3_deposit<2>;
         ASP_TRY(allow_dyn_lds((const void*)kern, lds));
         hipLaunchKernelGGL(kern, dim3(n_items), dim3(kDBlock), lds, st, g,
@@ -1177,49 +1167,27 @@ static int project3d(const float* x, const float* y, const float* z, const float
             w.nxl = std::min((bx0 + wb) * kBX, nx) - w.i_lo;
             w.nbx = std::min(wb, g.nbx - bx0);
             w.nb = w.nbx * g.nby * g.nbz;
-            // particle batches of < 2^31 (ASP_MAX_BATCH), halved while a pass would reach
-            // 2^31 records; batches after the first accumulate
-            long long B = 1LL << 30;
-            if (const char* e = getenv("ASP_MAX_BATCH")) B = std::max(1LL, atoll(e));
-            std::vector<std::pair<long long, long long>> todo;
-            for (long long a = ((n - 1) / B) * B; a >= 0; a -= B) todo.push_back({a, std::min(n, a + B)});
-            int passes = 0;
-            while (!todo.empty()) {
-                const auto [a, b] = todo.back();
-                todo.pop_back();
-                const int rc = cube_pass(ws, w, dx + a, dy + a, dz + a, dh + a, da + a, b - a,
-                                         kid, passes ? 1 : acc,
-                                         dout + (long long)w.i_lo * ny * g.nzl, st, agg);
-                if (rc == kRetSplit3) {
-                    if (b - a < 2)
-                        return fail(ASP_ERR_UNSUPPORTED, "one particle makes >= 2^31 records");
-                    todo.push_back({a + (b - a) / 2, b});
-                    todo.push_back({a, a + (b - a) / 2});
-                    continue;
-                }
-                ASP_TRY(rc);
-                ++passes;
-            }
+            // particle batches (for_batches); batches after the first accumulate
+            ASP_TRY(for_batches(n, [&](long long a, long long b, int i) {
+                return cube_pass(ws, w, dx + a, dy + a, dz + a, dh + a, da + a, b - a, kid,
+                                 i ? 1 : acc, dout + (long long)w.i_lo * ny * g.nzl, st, agg);
+            }));
         }
     }
     if (!dev) {
         ASP_HIP(hipMemcpyAsync(out, dout, nvox * sizeof(float), hipMemcpyDeviceToHost, st));
         ASP_HIP(hipStreamSynchronize(st));
     }
+    stats_clear(ws);  // (the wide count and the 2-D-only counters stay 0)
     ws.stats[0] = agg[0];
     ws.stats[1] = agg[1];
-    ws.stats[2] = 0;
     ws.stats[3] = kBrickVox;
     ws.stats[4] = (long long)g.nbx * g.nby * g.nbz;
     ws.stats[5] = n > 0 ? ws.h_counters[cChunk] : 0;
     ws.stats[6] = agg[2];
     ws.stats[7] = agg[3];
     ws.stats[8] = n > 0 ? 1 : 0;
-    for (int k = 9; k < kNStats; ++k) ws.stats[k] = 0;  // 2-D-only counters
-    if (&ws != &g_ws[device]) {  // asp_last_stats reads slot 0 (under its lock, as in 2-D)
-        std::lock_guard<std::mutex> lk(g_ws[device].mu);
-        std::copy(ws.stats, ws.stats + kNStats, g_ws[device].stats);
-    }
+    stats_publish(ws, device);
     return ws_end_.finish();
 }
 

@@ -82,6 +82,23 @@ def test_knn_small_and_edge_cases(gpu):
 
 
 @pytest.mark.gpu
+def test_knn_clears_the_last_maps_stats(gpu):
+    """asp_last_stats after a k-NN call describes that call: the counters of an earlier 2-D
+    map (how its records were scattered, the placement trials' runs) do not linger."""
+    from asp_amd.device import project2d, stats
+    from asp_amd.knn import knn_smoothing_lengths
+    from asp_amd.plummer import plummer_torch
+    d = plummer_torch(20_000, seed=1, h_law="pixel", extent=4.0, grid=256, device="cuda")
+    for _ in range(2):  # the second map's speculative scatter finds the first's buffers
+        project2d(d["x"], d["y"], d["h"], d["m"], image_size=(256, 256),
+                  extent=(-4.0, 4.0, -4.0, 4.0), kernel="cubic")
+    assert stats(0)["scatter_path"] == 1
+    knn_smoothing_lengths(_plummer(2_000, 8), 32)
+    st = stats(0)
+    assert st["scatter_path"] == 0 and st["placement_runs"] == 0, st
+
+
+@pytest.mark.gpu
 def test_knn_device_tensor_and_large(gpu):
     """2e6 Plummer particles (dense core + sparse halo), device-resident input."""
     import torch

@@ -2,7 +2,9 @@
 """Same-process A/B of cube settings (the record buffer keeps its placement across calls,
 so the scatter's placement mode cancels): 10^8 Plummer particles, physical h, 512^3
 Wendland-C2 cube, env knobs switched between calls, the cubes compared with the first
-setting's.  Usage: python tools/cube_ab.py 'ASP_CUBE_COMPACT=0' 'ASP_CUBE_COMPACT=1' ..."""
+setting's.  Usage: python tools/cube_ab.py 'ASP_CUBE_SGRP=2' 'ASP_CUBE_SGRP=1' ...
+(any knob the library reads per call; INTEGRATION.md lists them -- round 5's
+ASP_CUBE_COMPACT and ASP_CUBE_NBLK in the kept logs are no longer read)."""
 import os
 import sys
 
