@@ -44,11 +44,12 @@ EXPORTS = ("asp_version", "asp_last_error", "asp_device_count", "asp_project2d",
            "asp_project3d", "asp_kernel_eval", "asp_chunk_ranges", "asp_pixel_neighbours", "asp_ratio",
            "asp_profile", "asp_profile_stages", "asp_profile_read", "asp_last_stats",
            "asp_release", "asp_stage_particles", "asp_periodic", "asp_wrapped_distance",
-           "asp_knn_smoothing_lengths", "asp_table_interp3", "asp_table_interp")
+           "asp_knn_smoothing_lengths", "asp_table_interp3", "asp_table_interp", "asp_nearest")
 
 STAGES = ("memset", "count", "colscan", "tilescan", "scatter", "scale", "deposit", "merge",
           "wide", "ratio", "cube_count", "cube_colscan", "cube_tilescan", "cube_scatter",
-          "cube_deposit", "cube_merge", "gather", "knn_prep", "knn_search")
+          "cube_deposit", "cube_merge", "gather", "knn_prep", "knn_search", "nearest_prep",
+          "nearest_search")
 
 _lib = None
 
@@ -153,7 +154,9 @@ def lib():
     L.asp_table_interp.argtypes = ([_d, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_void_p),
                                     _d, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_double,
                                     C.c_int32, C.c_int32, _d, _d, _d, C.c_int32, C.c_void_p])
-    for name in ("asp_project2d", "asp_project2d_f64", "asp_pairs_begin", "asp_pairs_emit",
+    L.asp_nearest.argtypes = [_d, C.c_int64, _d, C.c_int64, C.POINTER(C.c_uint32), C.c_int32,
+                              C.c_double, _i32, _d, C.c_int32, C.c_int32, C.c_void_p]
+    for name in ("asp_nearest", "asp_project2d", "asp_project2d_f64", "asp_pairs_begin", "asp_pairs_emit",
                  "asp_pairs_end", "asp_project3d", "asp_kernel_eval", "asp_chunk_ranges",
                  "asp_pixel_neighbours", "asp_ratio", "asp_profile", "asp_profile_stages",
                  "asp_profile_read", "asp_last_stats", "asp_release", "asp_stage_particles",

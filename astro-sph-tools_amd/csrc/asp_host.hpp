@@ -71,7 +71,7 @@ struct Buf {
     size_t cap = 0;
 };
 
-constexpr int kStages = 19;
+constexpr int kStages = 21;
 constexpr int kNStats = 15;  // asp_last_stats
 constexpr int kMarks = 8;  // launches of one stage timed per call
 enum Stage {
@@ -80,7 +80,9 @@ enum Stage {
     // 3-D cube (asp_project3d)
     kS3Count = 10, kS3Colscan, kS3Tilescan, kS3Scatter, kS3Deposit, kS3Merge,
     kSGather = 16,  // 2-D gathered deposit of the large-record stream
-    kSKnnPrep = 17, kSKnnSearch = 18  // k-NN: keys / sort / tables; the search kernel
+    kSKnnPrep = 17, kSKnnSearch = 18,  // k-NN: keys / sort / tables; the search kernel
+    // asp_nearest: centre check / cell sort; the search (with the query sort, when on)
+    kSNearestPrep = 19, kSNearestSearch = 20
 };
 
 struct Workspace {
@@ -102,6 +104,10 @@ struct Workspace {
     // knn[10]: the suffix-minimum block minima of its scan, knn[11]: the ASP_KNN_COUNT
     // distance counters)
     Buf knn[12];
+    // asp_nearest: staged centres, member words, check counters, cell counts / cursors, cell
+    // starts, entries, scan scratch, the ASP_NEAREST_COUNT counter, staged queries, staged
+    // outputs, query sort keys, indices and scratch
+    Buf nearest[13];
     Buf in[5], out[2], hist, cmx, tile_total, tile_start, tile_k, items, merges, counters, recs,
         wide, slabs, morton, aux[6], iorder;
     Buf in64[4];     // asp_project2d_f64: the caller's fp64 arrays, resident for exact decisions
@@ -139,6 +145,7 @@ struct Workspace {
         for (auto& b : out) v.push_back(&b);
         for (auto& b : aux) v.push_back(&b);
         for (auto& b : knn) v.push_back(&b);
+        for (auto& b : nearest) v.push_back(&b);
         for (auto& b : in64) v.push_back(&b);
         for (auto& b : pairs) v.push_back(&b);
         for (auto& b : inw) v.push_back(&b);

@@ -350,6 +350,40 @@ int asp_knn_smoothing_lengths(const double *positions, int64_t n, int32_t k, dou
                               int32_t flags, int32_t device, void *stream);
 
 /*
+ * Nearest halo centre of every particle in a periodic box: replaces the scipy query of
+ * _scripts/find_nearest_haloes.py:196-221, KDTree(halo_centres[mask], boxsize=L).query(
+ * positions), once per minimum-halo-mass cut -- here every cut ("set") in one call.
+ *   positions (n, 3) float64 row-major, any finite values; centres (m, 3) float64, every
+ *   coordinate in [0, L), L = box_width; member[j] bit s set: centre j belongs to set s
+ *   (member NULL: every centre in set 0, nsets = 1); 1 <= nsets <= 8; m < 2^31 and fewer
+ *   than 2^31 memberships over all sets (else ASP_ERR_UNSUPPORTED); index int32 and distance
+ *   float64, both (nsets, n) set-major.
+ * Arithmetic (scipy's, fp64, in this order, no fused multiply-add): per axis the query is
+ * wrapped, w = x - floor(x / L) * L, then w >= L -> w - L, w < 0 -> w + L; for a centre c,
+ * d = w - c, d < -L/2 -> L + d, else d > L/2 -> d - L; d2 = ((dx dx + dy dy) + dz dz).
+ * distance[s, i] = sqrt(min d2 over the centres of set s): bit-identical to scipy's
+ * query(...)[0].  index[s, i] = the minimising centre's position in `centres` (not in the
+ * subset, so np.take(halo_ids, index) needs no masked copy); exact ties in d2 go to the
+ * lowest position (scipy's tie order is unspecified).  An empty set gives index -1 and
+ * distance +inf (the values the script writes for a cut without haloes).
+ * Differences from scipy: a query row with a non-finite coordinate gives index -1 and
+ * distance NaN for that row only (scipy raises for the whole array).  A centre outside
+ * [0, L) or non-finite is ASP_ERR_INVALID, as scipy refuses such a tree; asp_last_error
+ * names the condition.  box_width not finite or <= 0, nsets outside 1..8, member NULL with
+ * nsets > 1, n < 0, m < 0, NULL arrays with non-zero sizes: ASP_ERR_INVALID before any
+ * device work.  Any n >= 0 runs in one call (batched internally).
+ * Host pointers, staged through the device workspace, unless ASP_F_DEVICE_PTRS (then every
+ * pointer is a device pointer and the work is ordered on `stream`; the call still waits
+ * for the centre check).  Environment (read per call): ASP_NEAREST_SORT (1, the default,
+ * searches the queries in the order of their cell key, 0 in the caller's order; same
+ * results), ASP_NEAREST_PRUNE (0 scans every cell of every shell; same results),
+ * ASP_NEAREST_COUNT (diagnostic: asp_last_stats[9] = distances evaluated).
+ */
+int asp_nearest(const double *positions, int64_t n, const double *centres, int64_t m,
+                const uint32_t *member, int32_t nsets, double box_width, int32_t *index,
+                double *distance, int32_t flags, int32_t device, void *stream);
+
+/*
  * Ionisation-table interpolation: replaces the scipy
  * RegularGridInterpolator of data_structures/_IonisationTable.py:44-58 (linear,
  * bounds_error=False, fill_value=-inf; the HM01 tables of
@@ -397,7 +431,9 @@ int asp_table_interp(const double *table, int32_t ndim, const int32_t *shape,
  * was kept, 2 record-placement trials, 3 the speculative scatter found the buffers too
  * small and was relaunched after growing them, 0 one plain launch; the largest code over
  * the passes), stats[14] scatter runs of the placement trials.  Images of more than 4096
- * tiles and batched calls: the sums over all passes.
+ * tiles and batched calls: the sums over all passes.  After asp_knn_smoothing_lengths
+ * (ASP_KNN_COUNT) and asp_nearest (ASP_NEAREST_COUNT) the words describe that call: stats[9]
+ * = distances evaluated (asp_nearest: over all queries and sets), the map counters 0.
  */
 int asp_last_stats(int32_t device, int64_t *stats, int32_t nstats);
 
@@ -407,7 +443,9 @@ int asp_last_stats(int32_t device, int64_t *stats, int32_t nstats);
  * summed milliseconds and the number of launches since the last reset.  Stages:
  * 0 memset, 1 count, 2 colscan, 3 tilescan, 4 scatter, 5 scale, 6 deposit, 7 merge,
  * 8 wide, 9 ratio; cube (asp_project3d): 10 count, 11 colscan, 12 tilescan, 13 scatter,
- * 14 deposit, 15 merge; 16 gather (2-D gathered deposit of the large-record stream).
+ * 14 deposit, 15 merge; 16 gather (2-D gathered deposit of the large-record stream);
+ * 17 knn_prep, 18 knn_search (asp_knn_smoothing_lengths); 19 nearest_prep, 20 nearest_search
+ * (asp_nearest: the centre check and cell sort; the search, with the query sort when on).
  */
 int asp_profile(int32_t device, int32_t enable);
 /* As asp_profile(device, 1), but events only around the stages whose bit is set in
