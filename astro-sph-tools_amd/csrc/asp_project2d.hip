@@ -1508,6 +1508,10 @@ __global__ __launch_bounds__(kGatherThreads) void k_wide(
                 clip(P.b, X0, Y0, TW, TH)) {
                 P.u = (float)(src_u(s, p, P.u) - corner_x(g, X0));  // tile-local frame
                 P.v = (float)(src_v(s, p, P.v) - corner_y(g, Y0));
+                // the band of THIS frame (|P.u| <= 64 pitches + 2h, offsets < 64 pitches), as
+                // K4g's: prep_record's g.mg band is the absolute frame's, and through
+                // edge_dead2 it would put |corner| / 2h into the dead zone
+                set_band(P, rec_thr(P.h), rec_band(g.mgl, P.h));
                 mine = make_gentry(P, X0, Y0, kShapeScale<KID>);
             }
         }
@@ -1601,6 +1605,7 @@ __global__ __launch_bounds__(kBlock) void k_evals(Grid g, int kid, Src64 s,
                 clip(P.b, X0, Y0, TW, TH)) {
                 const unsigned box = (unsigned)(P.b.x0 - X0) | ((unsigned)(P.b.x1 - X0) << 8) |
                                      ((unsigned)(P.b.y0 - Y0) << 16) | ((unsigned)(P.b.y1 - Y0) << 24);
+                set_band(P, rec_thr(P.h), rec_band(g.mgl, P.h));  // the tile frame's, as K6
                 c2 += gather_slots(g, kid, box, (float)(src_u(s, p, P.u) - corner_x(g, X0)),
                                    (float)(src_v(s, p, P.v) - corner_y(g, Y0)), P.hi);
             }

@@ -7,6 +7,15 @@ alone: on every input set of tests/test_gpu_path_values.py and both kernels
   class in turn (the gathered, wide and wave-walked classes included);
 * the global-peak bar of tests/test_gpu_parity.py accepts the wide class scaled by 1.2 on
   ``test_wide_particles``' own inputs -- the gap the per-pixel bar closes.
+
+At the offset windows (value_bar.WINDOWS: zoom maps far from the origin, the same bar)
+
+* a float32 evaluation in LOCAL frames -- the device's arithmetic -- passes at every window;
+* the absolute-frame evaluation fl32(u) - fl32(X) is rejected wherever u or X is off the
+  fp32 lattice: the raw fp64 set on ``box`` and ``far_negative``, any set on ``box_offgrid``;
+* the edge forms' dead zone taken from the local frames' bound passes, and
+  taken from max |corner| for the wide class alone is rejected;
+* every class scaled by 1 + 1e-3 is rejected on ``box``.
 """
 import numpy as np
 import pytest
@@ -77,6 +86,156 @@ def test_stamps(oracle, kernel):
             if where != "outside":  # (there a small disc shows only its tail, W < 0.1 W(0))
                 with pytest.raises(AssertionError, match="worst err/E"):
                     vb.assert_terms_close(r * (1 + 1e-3), r, E)
+
+
+# ------------------------------------------------- offset windows (value_bar.WINDOWS)
+def _window_evaluations(oracle, kernel, window):
+    """The local-frame fp32 evaluation of the window's mixed set (amplitudes a): plain, with
+    every record's dead zone from mgl, and with the wide class's from mg = max |corner|."""
+    def make():
+        s = vb.mixed_set(oracle, kernel, window)
+        ext = vb.window_ext(window)
+        mg, mgl = vb.frame_bounds(vb.SIZE2D, ext)
+        tau_l = vb.dead_zone_tau(mgl, s["h"])
+        wide = s["cls"] == s["names"].index("h40-120")
+        tau_g = np.where(wide, vb.dead_zone_tau(mg, s["h"]), tau_l)
+        assert np.all(tau_g[wide] > 0)  # the dead zone is on (tau < 2^-4) for every wide h
+        (plain, dead_l, dead_g), cnt = vb.eval_f32_local_2d(s, s["a"], kernel, vb.SIZE2D, ext,
+                                                           taus=(None, tau_l, tau_g))
+        return dict(plain=plain, dead_l=dead_l, dead_g=dead_g, cnt=cnt)
+    return vb._cached(("window_evals", kernel, window), make)
+
+
+@pytest.mark.parametrize("kernel", vb.KERNELS)
+@pytest.mark.parametrize("window", vb.WINDOW_NAMES)
+def test_window_local_frame_passes(oracle, kernel, window):
+    """The device's arithmetic (local frames) stays inside the bar at every window: the
+    inputs chosen keep a correct implementation inside a bar that has no |corner| term."""
+    ref = vb.reference2d(oracle, kernel, window=window)
+    ev = _window_evaluations(oracle, kernel, window)
+    assert np.array_equal(ev["cnt"], ref["cnt"])
+    worst = vb.assert_terms_close(ev["plain"], ref["r1"], ref["E1"], ref["by_class1"])
+    assert worst > 0.0
+    print(f"VALUE_BAR cpu local frame {window} {kernel}: worst err/E = {worst:.3f}")
+
+
+@pytest.mark.parametrize("kernel", vb.KERNELS)
+@pytest.mark.parametrize("window,raw", [("box", True), ("box_offgrid", False),
+                                        ("far_negative", True)],
+                         ids=["box", "box_offgrid", "far_negative"])
+def test_window_absolute_frame_is_rejected(oracle, kernel, window, raw):
+    """eval_f32_2d forms fl32(u) - fl32(X) in absolute coordinates; the bar must catch it
+    wherever that arithmetic loses something, i.e. wherever u or X is off the fp32 lattice.
+
+    ``box`` and ``far_negative`` (corners exact in fp32) with the RAW fp64 set, the inputs of
+    the fp64 entry points: fl32(u) moves a position by up to half the lattice step, 1/16
+    pitch near 67 and 1/8 pitch near -1000, where a local frame formed from the fp64 value
+    keeps it -- the local-frame evaluation of the same raw set passes the same bar (with
+    F64_INPUT_ULPS for the rounding of h and a, which both evaluations do).
+    ``box_offgrid`` with the fp32 set: the positions are exact, the corners X round to the
+    lattice near 67 (2^-17, 1/8 pitch) and are off by up to 1/16 pitch.
+
+    (The fp32 set on ``box`` cannot show this: the pitch 2^-14 is a whole multiple of the
+    lattice 2^-17 and x_min lies on it, so every corner and every fp32 position is exact and
+    the absolute frame carries no error there at all.)"""
+    s = vb.mixed_set(oracle, kernel, window, raw)
+    ref = vb.reference2d(oracle, kernel, window=window, raw=raw)
+    ext = vb.window_ext(window)
+    (loc,), cnt = vb.eval_f32_local_2d(s, s["a"], kernel, vb.SIZE2D, ext)
+    assert np.array_equal(cnt, ref["cnt"])
+    worst = vb.assert_terms_close(loc, ref["r1"], ref["E1"], ref["by_class1"])
+    print(f"VALUE_BAR cpu local frame {window} raw={raw} {kernel}: worst err/E = {worst:.3f}")
+    g, cnt = vb.eval_f32_2d(s, s["a"], kernel, vb.SIZE2D, ext)
+    assert np.array_equal(cnt, ref["cnt"])
+    with pytest.raises(AssertionError, match="worst err/E") as bad:
+        vb.assert_terms_close(g, ref["r1"], ref["E1"], ref["by_class1"])
+    print(f"VALUE_BAR cpu absolute frame {window} raw={raw} {kernel}: rejected, "
+          + str(bad.value).split(" at pixel")[0])
+
+
+@pytest.mark.parametrize("kernel", vb.KERNELS)
+@pytest.mark.parametrize("window", vb.WINDOW_NAMES)
+def test_window_dead_zone_frame(oracle, kernel, window):
+    """The edge forms' dead zone tau = band / (2 thr) + 2^-20: taken from the local frames'
+    bound mgl (128 pitches) it stays inside the bar; taken from mg = max |corner| for the
+    wide class alone -- what a wide path that keeps prep_record's absolute-frame band
+    evaluates -- it is rejected, and the report names that class."""
+    ref = vb.reference2d(oracle, kernel, window=window)
+    ev = _window_evaluations(oracle, kernel, window)
+    worst = vb.assert_terms_close(ev["dead_l"], ref["r1"], ref["E1"], ref["by_class1"])
+    print(f"VALUE_BAR cpu dead zone mgl {window} {kernel}: worst err/E = {worst:.3f}")
+    with pytest.raises(AssertionError, match="worst err/E.*dominated by class h40-120"):
+        vb.assert_terms_close(ev["dead_g"], ref["r1"], ref["E1"], ref["by_class1"])
+
+
+@pytest.mark.parametrize("kernel", vb.KERNELS)
+def test_window_scaled_class_is_rejected(oracle, kernel):
+    s = vb.mixed_set(oracle, kernel, "box")
+    ref = vb.reference2d(oracle, kernel, window="box")
+    for k, name in enumerate(s["names"]):
+        bad = ref["r1"] + 1e-3 * vb.class_map2d(oracle, s, s["a"], kernel, k,
+                                                ext=vb.window_ext("box"))
+        with pytest.raises(AssertionError, match="worst err/E"):
+            vb.assert_terms_close(bad, ref["r1"], ref["E1"], ref["by_class1"])
+        with pytest.raises(AssertionError, match="worst err/E"):  # the fixed-point bar too
+            vb.assert_terms_close(bad, ref["r1"], ref["E1"], ref["by_class1"], floor=ref["F1"])
+
+
+def test_window_sets_keep_their_local_positions(oracle):
+    """The windows' sets are the default set's draws: the same classes, h in pitches and
+    equal-peak amplitudes, fp32-representable; the raw set is not rounded."""
+    base = vb.mixed_set(oracle, "cubic")
+    for window in vb.WINDOW_NAMES:
+        ext = vb.window_ext(window)
+        pitch = vb.pitch2d(vb.SIZE2D, ext)
+        s, raw = vb.mixed_set(oracle, "cubic", window), vb.mixed_set(oracle, "cubic", window, True)
+        assert np.array_equal(s["cls"], base["cls"])
+        for key in ("u", "v", "h", "a", "a0"):
+            assert np.array_equal(s[key], vb.f32(s[key])), key
+        assert np.any(raw["u"] != vb.f32(raw["u"])) and np.any(raw["h"] != vb.f32(raw["h"]))
+        np.testing.assert_allclose(s["h"] / pitch, base["h"] / vb.PITCH2D, rtol=3e-7)
+        lu = (raw["u"] - ext[0]) / ((ext[1] - ext[0]) / 256)
+        np.testing.assert_allclose(lu, (base["u"] + 1.0) / vb.PITCH2D, atol=1e-4)  # pitches
+        peak = s["a"] * vb.w0(oracle, "cubic", s["h"])
+        assert 0.49 < peak.min() and peak.max() < 1.51
+
+
+def test_window_stamps(oracle):
+    """The stamps at every window: reference equals the oracle, the local-frame evaluation
+    passes the particle's own term."""
+    kernel = "wendland_c2"
+    for window in vb.WINDOW_NAMES:
+        ext = vb.window_ext(window)
+        for path, h_px, *_ in vb.STAMP_PATHS:
+            for where in vb.STAMP_POSITIONS:
+                u, v, h, a = vb.stamp_particle(oracle, kernel, h_px, where, window)
+                assert (u, v, h, a) == tuple(float(vb.f32(t)) for t in (u, v, h, a))
+                r, E = vb.stamp_reference(oracle, kernel, u, v, h, a, vb.SIZE2D, ext)
+                assert np.count_nonzero(r) > 0, (window, path, where)
+                one = dict(u=np.array([u]), v=np.array([v]), h=np.array([h]))
+                want, _ = oracle.project_scatter(one["u"], one["v"], one["h"], [a], None,
+                                                 vb.SIZE2D, vb.CHUNK, *ext, kernel=kernel)
+                assert np.array_equal(r != 0, want != 0)
+                np.testing.assert_allclose(r, want, rtol=1e-9, atol=1e-10)
+                (g,), _ = vb.eval_f32_local_2d(one, [a], kernel, vb.SIZE2D, ext)
+                vb.assert_terms_close(g, r, E)
+
+
+def test_f64_input_term():
+    """F64_INPUT_ULPS bounds the effect of rounding h and a to fp32 on a W(r, h), measured
+    on the fp64 kernel itself at the worst roundings (relative 2^-24 each)."""
+    q = np.linspace(0.0, 2.0, 4001)
+    for kernel in vb.KERNELS:
+        h, a = 0.37, 1.3
+        w_0 = a * vb.kernel_f64(kernel, np.zeros(1), np.array([h]))[0]
+        for sh in (-1.0, 1.0):
+            for sa in (-1.0, 1.0):
+                hh, aa = h * (1 + sh * vb.U24), a * (1 + sa * vb.U24)
+                d = np.abs(aa * vb.kernel_f64(kernel, q * h, hh)
+                           - a * vb.kernel_f64(kernel, q * h, h))
+                assert d.max() <= vb.F64_INPUT_ULPS * vb.U24 * w_0
+                if sh != sa:  # (opposite signs add up at q = 0: the count is not slack)
+                    assert d.max() >= 3.9 * vb.U24 * w_0
 
 
 def test_report_names_pixel_and_class(oracle):

@@ -44,6 +44,11 @@ Where the constants come from (none of them from the device's output):
 * ``deterministic=True`` (int64 fixed point) adds the header's documented term, bounded
   from above by F = 2^-37 n max_p(|a_p| W(0, h_p)), n the call's particle count.
 
+* The bar has no term in |u| or |corner|: DESIGN §3 claims the pair error is 2^-24 of the
+  pair distance.  WINDOWS puts the same sets at zoom windows 1e5 .. 1e7 pitches from the
+  origin to test exactly that; for the raw-fp64 entry points F64_INPUT_ULPS (derived where
+  it is defined) covers the device's own rounding of h and a.
+
 ``assert_terms_close(g, r, E)`` asserts g == 0 exactly where r == 0 and |g - r| <= E at
 every pixel; a failure reports the worst err/E, its pixel and the class of particle
 that dominates E there.
@@ -74,6 +79,35 @@ CLASSES_2D = (("h0.55-0.75", 0.55, 0.75, 1500), ("h0.8-1.2", 0.8, 1.2, 800),
 CLUMP = ("clump", 0.55, 1.2, 2000)  # sigma = 2 px about the centre of tile (2, 1)
 CLUMP_CENTRE = (0.25, -0.25)
 WIDE_TILES = "4"  # ASP_WIDE_TILES for the 2-D sets: the h40-120 class takes the wide path
+
+# Offset windows: zoom maps far from the origin, (name, ext) on SIZE2D with
+# chunk CHUNK.  The sets keep their LOCAL positions -- the same rng draws, class table,
+# clump and stamp positions, in pixel pitches from the window's corner -- mapped as
+# x_min + local_pitches * pitch, then rounded to fp32 for the fp32 entry points and kept
+# raw for the fp64 ones.  The bar is the same: it has no |corner| term.
+#   box          corners and pitch (2^-14) exact in fp32, |corner| / pitch = 1.1e6; fp32
+#                positions near 67 lie on a 2^-17 lattice, 1/8 pitch (1/64 pitch in v)
+#   box_offgrid  neither the corners nor the pitch are fp32-representable
+#   far_negative pitch 2^-12; fp32 positions near -1000 lie on a 2^-14 lattice, 1/4 pitch
+#                in u, while v in [0, 2^-4) is fine-grained (2^-28 or finer, <= 2^-16
+#                pitch): |u| is large and negative, v near 0, so mg is asymmetric
+WINDOWS = (("box", (67.25, 67.25 + 2.0 ** -6, 12.5, 12.5 + 2.0 ** -6)),
+           ("box_offgrid", (67.3, 67.3157, 12.1, 12.1157)),
+           ("far_negative", (-1000.5, -1000.5 + 2.0 ** -4, 0.0, 2.0 ** -4)))
+WINDOW_NAMES = tuple(w[0] for w in WINDOWS)
+CUBE_SHIFT = (67.25, 12.5, 331.0)  # the cube's offset: EXT3D moved by it (corners exact)
+
+# The raw-fp64 entry points (asp_project2d_f64 / _props_f64): r is the oracle on the raw
+# fp64 arrays, and the device additionally rounds h and a to fp32 once each (k_to_f32,
+# round to nearest: relative error <= 2^-24 = 1 u each) before term_coef / kernel_norm64
+# and the shapes read them.  In units of u = 2^-24 of |a| W(0):
+#   - a -> fl32(a): the coefficient is linear in a                              1 u
+#   - h -> fl32(h) through the coefficient a K / h^3 (kernel_norm64 cubes it)   3 u
+#   - h -> fl32(h) through q = r / h: a relative error u of q moves f by
+#     q |f'(q)| u, max q |f'(q)| = 0.79 (see ALPHA)                          0.79 u
+# 4.79 u, taken as 5.  No coordinate term: the local coordinates are formed from the
+# resident fp64 positions (src_u / src_v) and rounded once, which eps_p already holds.
+F64_INPUT_ULPS = 5.0
 
 SIZE3D = (48, 40, 64)
 EXT3D = (-2.0, 2.0, -2.0, 2.0, -2.0, 2.0)
@@ -111,32 +145,63 @@ def _cached(key, make):
     return _cache[key]
 
 
-def mixed_set(oracle, kernel):
+def window_ext(window):
+    """The extent of a window of WINDOWS by name (None: EXT2D)."""
+    return EXT2D if window is None else dict(WINDOWS)[window]
+
+
+def _placer(window):
+    """(place_u, place_v, pitch): maps of the sets' EXT2D coordinates into the window --
+    the identity for None, else x_min + local_pitches * pitch with local_pitches =
+    (w + 1) / PITCH2D -- and the pitch the h classes are scaled with."""
+    if window is None:
+        return (lambda w: w), (lambda w: w), PITCH2D
+    ext = window_ext(window)
+    psx, psy = (ext[1] - ext[0]) / SIZE2D[0], (ext[3] - ext[2]) / SIZE2D[0]
+    return ((lambda w: ext[0] + ((np.asarray(w) + 1.0) / PITCH2D) * psx),
+            (lambda w: ext[2] + ((np.asarray(w) + 1.0) / PITCH2D) * psy), max(psx, psy))
+
+
+def mixed_set(oracle, kernel, window=None, raw=False):
     """The 2-D mixed set: every class of CLASSES_2D uniform in the extent plus the clump.
-    Keys u, v, h, a, T, a0 (= fl32(a T)), cls (class index), names."""
+    Keys u, v, h, a, T, a0 (= fl32(a T)), cls (class index), names.  ``window``: the same
+    local positions and h (in pixel pitches) at that window of WINDOWS.  ``raw``: nothing is
+    rounded to fp32 (the inputs of the fp64 entry points; a = U(0.5, 1.5) / W(0, h) on the
+    raw h, a0 = a T)."""
     def make():
+        pu, pv, pitch = _placer(window)
+        rnd = (lambda t: np.asarray(t, np.float64)) if raw else f32
         rng = np.random.default_rng(20)
         u, v, h, cls = [], [], [], []
         for k, (_, lo, hi, n) in enumerate(CLASSES_2D + (CLUMP,)):
             if k < len(CLASSES_2D):
-                u.append(rng.uniform(-1.0, 1.0, n))
-                v.append(rng.uniform(-1.0, 1.0, n))
+                u.append(pu(rng.uniform(-1.0, 1.0, n)))
+                v.append(pv(rng.uniform(-1.0, 1.0, n)))
             else:
-                u.append(rng.normal(CLUMP_CENTRE[0], 2 * PITCH2D, n))
-                v.append(rng.normal(CLUMP_CENTRE[1], 2 * PITCH2D, n))
-            h.append(rng.uniform(lo, hi, n) * PITCH2D)
+                u.append(pu(rng.normal(CLUMP_CENTRE[0], 2 * PITCH2D, n)))
+                v.append(pv(rng.normal(CLUMP_CENTRE[1], 2 * PITCH2D, n)))
+            h.append(rng.uniform(lo, hi, n) * pitch)
             cls.append(np.full(n, k))
-        u, v, h = (f32(np.concatenate(t)) for t in (u, v, h))
-        a = f32(rng.uniform(0.5, 1.5, h.size) / w0(oracle, kernel, h))
-        T = f32(rng.uniform(1.0, 3.0, h.size))
-        return dict(u=u, v=v, h=h, a=a, T=T, a0=f32(a * T), cls=np.concatenate(cls),
+        u, v, h = (rnd(np.concatenate(t)) for t in (u, v, h))
+        a = rnd(rng.uniform(0.5, 1.5, h.size) / w0(oracle, kernel, h))
+        T = rnd(rng.uniform(1.0, 3.0, h.size))
+        return dict(u=u, v=v, h=h, a=a, T=T, a0=rnd(a * T), cls=np.concatenate(cls),
                     names=[c[0] for c in CLASSES_2D + (CLUMP,)])
-    return _cached(("mixed", kernel), make)
+    key = ("mixed", kernel) if window is None and not raw else ("mixed", kernel, window, raw)
+    return _cached(key, make)
 
 
-def cube_set(oracle, kernel):
+def cube_ext(shift=None):
+    """EXT3D moved by ``shift`` = (sx, sy, sz)."""
+    if shift is None:
+        return EXT3D
+    return tuple(EXT3D[i] + shift[i // 2] for i in range(6))
+
+
+def cube_set(oracle, kernel, shift=None):
     """The cube set: positions uniform in +-2.2 (footprints clipped at the faces, some
-    missing the cube).  Keys x, y, z, h, a, cls, names."""
+    missing the cube).  Keys x, y, z, h, a, cls, names.  ``shift``: the same draws moved by
+    (sx, sy, sz), fp32-rounded after the shift."""
     def make():
         rng = np.random.default_rng(21)
         h, cls = [], []
@@ -144,11 +209,12 @@ def cube_set(oracle, kernel):
             h.append(rng.uniform(lo, hi, n) * PITCH3D)
             cls.append(np.full(n, k))
         h = f32(np.concatenate(h))
-        x, y, z = (f32(rng.uniform(-2.2, 2.2, h.size)) for _ in range(3))
+        sh = (0.0, 0.0, 0.0) if shift is None else shift
+        x, y, z = (f32(rng.uniform(-2.2, 2.2, h.size) + sh[d]) for d in range(3))
         a = f32(rng.uniform(0.5, 1.5, h.size) / w0(oracle, kernel, h))
         return dict(x=x, y=y, z=z, h=h, a=a, cls=np.concatenate(cls),
                     names=[c[0] for c in CLASSES_3D])
-    return _cached(("cube", kernel), make)
+    return _cached(("cube", kernel) if shift is None else ("cube", kernel, tuple(shift)), make)
 
 
 # Stamps: one particle per map.  (path name, h in pixel pitches, ASP_GATHER_MIN,
@@ -165,8 +231,19 @@ STAMP_PATHS = (("small3", 0.65, "65", str(1 << 30), "256", "small"),
 STAMP_POSITIONS = ("inside", "corner", "edge", "outside")
 
 
-def stamp_particle(oracle, kernel, h_px, where):
-    """(u, v, h, a) of one stamp, all fp32-representable."""
+def stamp_particle(oracle, kernel, h_px, where, window=None):
+    """(u, v, h, a) of one stamp, all fp32-representable.  ``window``: the same position in
+    pixel pitches from that window's corner."""
+    if window is not None:
+        ext = window_ext(window)
+        psx, psy = (ext[1] - ext[0]) / SIZE2D[0], (ext[3] - ext[2]) / SIZE2D[0]
+        h = float(f32(h_px * max(psx, psy)))
+        lu, lv = {"inside": (100.3, 37.6), "corner": (128.0, 128.0), "edge": (0.5, 150.25),
+                  "outside": (None, 90.4)}[where]
+        u = ext[0] - 1.5 * h if lu is None else ext[0] + lu * psx
+        u, v = float(f32(u)), float(f32(ext[2] + lv * psy))
+        a = float(f32(1.25 / w0(oracle, kernel, h)[0]))
+        return u, v, h, a
     h = float(f32(h_px * PITCH2D))
     if where == "inside":      # inside tile (1, 0), off the pixel corners
         u, v = -1.0 + 100.3 * PITCH2D, -1.0 + 37.6 * PITCH2D
@@ -192,12 +269,13 @@ def pitch3d(size, ext):
                (ext[5] - ext[4]) / size[2])
 
 
-def term_bound(oracle, kernel, h, a, pitch):
-    """e_p: the bound on the device's error in ONE term of particle p."""
+def term_bound(oracle, kernel, h, a, pitch, extra_ulps=0.0):
+    """e_p: the bound on the device's error in ONE term of particle p.  ``extra_ulps``:
+    F64_INPUT_ULPS where the device rounds raw fp64 h and a to fp32 itself."""
     h = np.atleast_1d(np.asarray(h, np.float64))
     a = np.atleast_1d(np.asarray(a, np.float64))
     eps = 2.0 ** -21 * (M_PITCHES * pitch + 2.0 * h)
-    return np.abs(a) * w0(oracle, kernel, h) * (BETA * eps / h + ALPHA * U24)
+    return np.abs(a) * w0(oracle, kernel, h) * (BETA * eps / h + (ALPHA + extra_ulps) * U24)
 
 
 def fixed_point_term(oracle, kernel, h, a):
@@ -206,9 +284,10 @@ def fixed_point_term(oracle, kernel, h, a):
     return 2.0 ** -37 * h.size * np.max(np.abs(a) * w0(oracle, kernel, h))
 
 
-def bar2d(oracle, s, a, kernel, size=SIZE2D, ext=EXT2D, chunk=CHUNK, deterministic=False):
+def bar2d(oracle, s, a, kernel, size=SIZE2D, ext=EXT2D, chunk=CHUNK, deterministic=False,
+          extra_ulps=0.0):
     """(E, by_class): E over the exact neighbour sets, and each class's share of it."""
-    e = term_bound(oracle, kernel, s["h"], a, pitch2d(size, ext))
+    e = term_bound(oracle, kernel, s["h"], a, pitch2d(size, ext), extra_ulps)
     by_class = {}
     for k, name in enumerate(s["names"]):
         m = s["cls"] == k
@@ -346,6 +425,90 @@ def eval_f32_2d(s, a, kernel, size=SIZE2D, ext=EXT2D, chunk=CHUNK):
     return out, cnt
 
 
+def _edge_shape_f32(kernel, q, tau):
+    """The edge-continuous form of f(q) (edge_shape2) in float32 with the dead
+    zone tau: t = clamp(1 - q/2), t^2 <- max(t t - tau^2, 0); cubic 2 (t^2 t - s^3 / 2)
+    with s = clamp(1 - q), Wendland (t^2)^2 (1 + 2q)."""
+    zero, one, two, half = (np.float32(c) for c in (0.0, 1.0, 2.0, 0.5))
+    tau = np.float32(tau)
+    t = np.clip(one - half * q, zero, one)
+    t2 = np.maximum(t * t - tau * tau, zero)
+    if kernel == "cubic":
+        sq = np.clip(one - q, zero, one)
+        return two * (t2 * t - half * (sq * sq * sq))
+    return (t2 * t2) * (one + two * q)
+
+
+def dead_zone_tau(M, h):
+    """tau of a record's dead zone from its decision band, in float32 as the device forms
+    it (rec_thr / rec_band / edge_dead2): band / (2 thr) + 2^-20, with M the bound on the
+    coordinates of the frame the band is taken for.  0 where the device leaves it off."""
+    M, h = np.float32(M), np.asarray(h, np.float32)
+    Da = np.abs(np.float32(2.0) * h)
+    eps = np.float32(2.0 ** -21) * (M + Da)
+    band = (np.float32(4.0) * Da * eps + np.float32(2.0) * eps * eps
+            + np.float32(2.0 ** -20) * Da * Da)
+    thr = Da * Da
+    lo, hi = thr - band, thr + band
+    tau = np.float32(0.5) * (hi - lo) / (hi + lo) + np.float32(2.0 ** -20)
+    return np.where(tau < np.float32(2.0 ** -4), tau, np.float32(0.0)).astype(np.float32)
+
+
+def frame_bounds(size, ext, tile=64):
+    """(mg, mgl) as the host sets them: the bound on |corner coordinate| in the absolute
+    frame, and in the records' local frames (2 tiles of the larger pitch)."""
+    nx, ny = size
+    psx, psy = (ext[1] - ext[0]) / nx, (ext[3] - ext[2]) / nx
+    mgl = 2.0 * tile * max(psx, psy)
+    mg = max(abs(ext[0]), abs(ext[0] + nx * psx), abs(ext[2]), abs(ext[2] + ny * psy), mgl)
+    return mg * (1.0 + 1e-6), mgl * (1.0 + 1e-6)
+
+
+def eval_f32_local_2d(s, a, kernel, size=SIZE2D, ext=EXT2D, chunk=CHUNK, taus=(None,), tile=64):
+    """The device's arithmetic in float32 NumPy: every pair in a LOCAL frame.  Per 64-pixel
+    tile, dx = fl32(u - X_tile_origin), formed in fp64 and rounded once, minus
+    fl32(k pitch), k the pixel's index within the tile; the rest as eval_f32_2d (fp32
+    operations, fp64 accumulation, the reference's neighbour sets).  One map per entry of
+    ``taus``: None is the plain shape, an array of per-particle tau (dead_zone_tau) the
+    edge-continuous form with that dead zone.  Returns (maps, neighbour counts)."""
+    nx, ny = size
+    x_min, x_max, y_min, y_max = ext
+    psx, psy, psyc = (x_max - x_min) / nx, (y_max - y_min) / nx, (y_max - y_min) / ny
+    ix, iy = np.arange(nx), np.arange(ny)
+    X = x_min + ix * psx
+    Y = y_min + iy * psy
+    X0, Y0 = X[(ix // tile) * tile], Y[(iy // tile) * tile]  # each pixel's tile origin
+    offx = ((ix % tile) * psx).astype(np.float32)
+    offy = ((iy % tile) * psy).astype(np.float32)
+    i0c, j0c = (ix // chunk) * chunk, (iy // chunk) * chunk
+    xlo, xhi = x_min + i0c * psx, x_min + np.minimum(i0c + chunk, nx) * psx
+    ylo, yhi = y_min + j0c * psyc, y_min + np.minimum(j0c + chunk, ny) * psyc
+    outs = [np.zeros((nx, ny)) for _ in taus]
+    cnt = np.zeros((nx, ny))
+    for p, (u, v, h, ap) in enumerate(zip(s["u"], s["v"], s["h"], a)):
+        h2 = 2.0 * h
+        i0 = max(0, int(np.floor((u - h2 - x_min) / psx)) - 2)
+        i1 = min(nx - 1, int(np.ceil((u + h2 - x_min) / psx)) + 2)
+        j0 = max(0, int(np.floor((v - h2 - y_min) / psy)) - 2)
+        j1 = min(ny - 1, int(np.ceil((v + h2 - y_min) / psy)) + 2)
+        if i0 > i1 or j0 > j1:
+            continue
+        si, sj = slice(i0, i1 + 1), slice(j0, j1 + 1)
+        dx, dy = u - X[si, None], v - Y[None, sj]
+        inc = (dx * dx + dy * dy) < h2 * h2
+        inc &= ((u >= xlo[si] - h2) & (u < xhi[si] + h2))[:, None]
+        inc &= ((v >= ylo[sj] - h2) & (v < yhi[sj] + h2))[None, :]
+        dx32 = ((u - X0[si]).astype(np.float32) - offx[si])[:, None]
+        dy32 = ((v - Y0[sj]).astype(np.float32) - offy[sj])[None, :]
+        q = np.sqrt(dx32 * dx32 + dy32 * dy32) / np.float32(h)
+        coef = _coef_f32(kernel, ap, h)
+        for out, tau in zip(outs, taus):
+            f = _shape_f32(kernel, q) if tau is None else _edge_shape_f32(kernel, q, tau[p])
+            out[si, sj] += np.where(inc, (coef * f).astype(np.float64), 0.0)
+        cnt[si, sj] += inc
+    return outs, cnt
+
+
 def eval_f32_3d(s, kernel, size=SIZE3D, ext=EXT3D):
     """The cube's counterpart of eval_f32_2d (each axis its own pitch, no cull)."""
     n = size
@@ -379,34 +542,42 @@ def eval_f32_3d(s, kernel, size=SIZE3D, ext=EXT3D):
 
 
 # ------------------------------------------------------- shared references (cached)
-def reference2d(oracle, kernel, size=SIZE2D):
+def reference2d(oracle, kernel, size=SIZE2D, window=None, raw=False):
     """The mixed set's oracle maps and bars on ``size``: r0 / r1 (a0 = a T, a1 = a),
-    E0 / E1, by_class0 / by_class1, and the fixed-point terms F0 / F1."""
+    E0 / E1, by_class0 / by_class1, the fixed-point terms F0 / F1 and the neighbour counts
+    cnt.  ``window`` / ``raw``: as mixed_set; the raw set's bar carries F64_INPUT_ULPS."""
     def make():
-        s = mixed_set(oracle, kernel)
+        s = mixed_set(oracle, kernel, window, raw)
+        ext = window_ext(window)
+        extra = F64_INPUT_ULPS if raw else 0.0
         r0, r1 = oracle.project_scatter(s["u"], s["v"], s["h"], s["a0"], s["a"], size, CHUNK,
-                                        *EXT2D, kernel=kernel)
-        E0, c0 = bar2d(oracle, s, s["a0"], kernel, size)
-        E1, c1 = bar2d(oracle, s, s["a"], kernel, size)
-        return dict(r0=r0, r1=r1, E0=E0, E1=E1, by_class0=c0, by_class1=c1,
+                                        *ext, kernel=kernel)
+        E0, c0 = bar2d(oracle, s, s["a0"], kernel, size, ext, extra_ulps=extra)
+        E1, c1 = bar2d(oracle, s, s["a"], kernel, size, ext, extra_ulps=extra)
+        cnt, _ = oracle.project_scatter(s["u"], s["v"], s["h"], np.ones(s["h"].size), None, size,
+                                        CHUNK, *ext, kernel="indicator")
+        return dict(r0=r0, r1=r1, E0=E0, E1=E1, by_class0=c0, by_class1=c1, cnt=cnt,
                     F0=fixed_point_term(oracle, kernel, s["h"], s["a0"]),
                     F1=fixed_point_term(oracle, kernel, s["h"], s["a"]))
-    return _cached(("ref2d", kernel, size), make)
+    key = ("ref2d", kernel, size) if window is None and not raw else \
+        ("ref2d", kernel, size, window, raw)
+    return _cached(key, make)
 
 
-def reference3d(oracle, kernel):
+def reference3d(oracle, kernel, shift=None):
     def make():
-        s = cube_set(oracle, kernel)
-        r = oracle.project3d(s["x"], s["y"], s["z"], s["h"], s["a"], SIZE3D, EXT3D, kernel=kernel)
-        E, c = bar3d(oracle, s, kernel)
+        s = cube_set(oracle, kernel, shift)
+        ext = cube_ext(shift)
+        r = oracle.project3d(s["x"], s["y"], s["z"], s["h"], s["a"], SIZE3D, ext, kernel=kernel)
+        E, c = bar3d(oracle, s, kernel, ext=ext)
         return dict(r=r, E=E, by_class=c)
-    return _cached(("ref3d", kernel), make)
+    return _cached(("ref3d", kernel) if shift is None else ("ref3d", kernel, tuple(shift)), make)
 
 
-def class_map2d(oracle, s, a, kernel, k, size=SIZE2D):
+def class_map2d(oracle, s, a, kernel, k, size=SIZE2D, ext=EXT2D):
     m = s["cls"] == k
     return oracle.project_scatter(s["u"][m], s["v"][m], s["h"][m], np.asarray(a)[m], None, size,
-                                  CHUNK, *EXT2D, kernel=kernel)[0]
+                                  CHUNK, *ext, kernel=kernel)[0]
 
 
 def class_map3d(oracle, s, kernel, k):
