@@ -33,6 +33,12 @@ constexpr int kBlock = 256;        // threads per workgroup for streaming kernel
 #define ASP_DEP_BLOCK 512
 #endif
 constexpr int kDepBlock = ASP_DEP_BLOCK;  // deposit workgroup (8 waves; 2 per CU)
+// K4's lane <-> record order: 1 = every wave orders a pool of its records by the LDS bank
+// pair of their base word ("LDS bank conflicts in K4"); 0 = lane t takes
+// record base + t (the order before that; kept for same-box A/B builds).
+#ifndef ASP_DEP_ORDER
+#define ASP_DEP_ORDER 1
+#endif
 constexpr int kTile = 64;          // GPU tile edge in pixels
 constexpr int kTileShift = 6;
 constexpr int kRow = kTile + 1;    // LDS tile row stride in words (one pad word per row)

@@ -1236,6 +1236,92 @@ __device__ __forceinline__ void gather_emit(const Grid& g, const GAcc<NOUT, ACC>
     }
 }
 
+// ----------------------------------------------------------------------------------
+// Bank-balanced record order for K4 (ASP_DEP_ORDER).  A ds_add_f64 is served in four
+// contiguous 16-lane groups, and lanes of a group whose 8-B words share a bank pair (word
+// index mod 16) take one LDS pass each (measured: tools/microbench/lds.hip `dep`,
+// profiles/deposit_order/).  The lane-per-record body adds the same constant i * kRow + j
+// to every lane's base word, so lanes that are conflict-free at the base word are so for
+// all 18 adds.  Each wave therefore takes a contiguous pool of kPool records of the item,
+// loads only their box words, and orders the pool "by level": first one record of every
+// bank pair that has any, then the second ones, ... -- 16 consecutive positions hold
+// distinct bank pairs wherever a level is full.  Lane l of batch j takes the record at
+// position 64 j + l and loads it by index (the pool's lines are in L2 from the key loads).
+// ----------------------------------------------------------------------------------
+constexpr int kPoolBatches = 2;
+constexpr int kPool = 64 * kPoolBatches;  // <= 256: pool indices are bytes
+static_assert(kRow % 16 == 1, "bank pair of pix(x, y) is (x + y) mod 16");
+struct OrderLds {  // per wave
+    int cnt[16];               // records per bank pair
+    unsigned lvl[64];          // level r: positions before it << 16 | bank pairs present
+    unsigned char tab[kPool];  // position -> pool index, [lane][batch]
+};
+
+__device__ __forceinline__ void wave_lds_sync() {  // LDS written by other lanes of the wave
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// key[j]: packed box word of pool record 64 j + lane; the first n records are live.
+// Returns the pool indices this lane takes in batches 0 .. kPoolBatches-1, one byte each
+// (meaningful for positions 64 j + lane < n only).
+__device__ __forceinline__ unsigned order_pool(const unsigned (&key)[kPoolBatches], int n,
+                                               OrderLds& w, int lane) {
+    if (lane < 16) w.cnt[lane] = 0;
+    wave_lds_sync();
+    int bank[kPoolBatches], r[kPoolBatches];  // bank pair; rank among the pool's records of it
+    bool big = false;
+#pragma unroll
+    for (int j = 0; j < kPoolBatches; ++j) {
+        bank[j] = (int)(((key[j] & 255u) + ((key[j] >> 16) & 255u)) & 15u);
+        r[j] = j * 64 + lane < n ? atomicAdd(&w.cnt[bank[j]], 1) : 0;
+        big |= r[j] >= 64;
+    }
+    wave_lds_sync();
+    const int c = w.cnt[lane & 15];
+    {   // lane r: level r starts at T = sum_b min(cnt[b], r) and holds the banks with cnt > r
+        int T = 0;
+        unsigned m = 0;
+#pragma unroll
+        for (int b = 0; b < 16; ++b) {
+            const int cb = __builtin_amdgcn_readlane(c, b);
+            T += min(cb, lane);
+            m |= cb > lane ? 1u << b : 0u;
+        }
+        w.lvl[lane] = (unsigned)T << 16 | m;
+    }
+    wave_lds_sync();
+    int pos[kPoolBatches];
+    if (__ballot(big)) {  // a bank pair with more than 64 records: the same sums per record
+#pragma unroll
+        for (int j = 0; j < kPoolBatches; ++j) {
+            int p = 0;
+            for (int b = 0; b < 16; ++b) {
+                const int cb = __builtin_amdgcn_readlane(c, b);
+                p += min(cb, r[j]) + (b < bank[j] && cb > r[j] ? 1 : 0);
+            }
+            pos[j] = p;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < kPoolBatches; ++j) {
+            const unsigned e = w.lvl[r[j]];
+            pos[j] = (int)(e >> 16) + __popc(e & ((1u << bank[j]) - 1u));
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < kPoolBatches; ++j)
+        if (j * 64 + lane < n)
+            w.tab[(pos[j] & 63) * kPoolBatches + (pos[j] >> 6)] = (unsigned char)(j * 64 + lane);
+    wave_lds_sync();
+    unsigned idx = 0u;
+#pragma unroll
+    for (int j = 0; j < kPoolBatches; ++j) idx |= (unsigned)w.tab[lane * kPoolBatches + j] << (8 * j);
+    wave_lds_sync();
+    return idx;
+}
+
 // Which records take which path in K4 (clipped box w x h pixels).
 __device__ __forceinline__ bool is_small(int bw, int bh) { return bw <= 4 && bh <= 4; }
 
@@ -1260,6 +1346,10 @@ __global__ __launch_bounds__(kDepBlock) __attribute__((amdgpu_waves_per_eu(4))) 
     float* xt = (float*)(acc + NOUT * kTileWords);
     float* yt = xt + kTile;
     __shared__ int defer_lds[kDepBlock / 64][kDeferCap];
+    // Two maps only: with one map a record has 9 adds, not 18, and ordering it costs more
+    // than its conflicts (10^7 -> 2048^2 surface map: deposit 0.106 -> 0.127 ms ordered).
+    constexpr bool kOrdered = ASP_DEP_ORDER && NOUT == 2;
+    __shared__ OrderLds order_lds[kOrdered ? kDepBlock / 64 : 1];
     const Item it = items[order[blockIdx.x]];  // largest items first (k_tilescan)
     if (it.mode != 0) return;  // the large stream's (K4g)
     int tx = it.tile / g.nty, ty = it.tile - (it.tile / g.nty) * g.nty;
@@ -1336,21 +1426,76 @@ __global__ __launch_bounds__(kDepBlock) __attribute__((amdgpu_waves_per_eu(4))) 
         if constexpr (EXT) e = ext[i];
         else e = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     };
-    load_rec(recs, it.start + min((int)threadIdx.x, last), r0, r1);
-    load_ext(it.start + min((int)threadIdx.x, last), re);
-    load_rec(recs, it.start + min((int)threadIdx.x + kDepBlock, last), q0, q1);
-    load_ext(it.start + min((int)threadIdx.x + kDepBlock, last), qe);
-    for (int base = 0; base < it.count; base += kDepBlock) {
-        float4 n0, n1, ne;
-        load_rec(recs, it.start + min(base + (int)threadIdx.x + 2 * kDepBlock, last), n0, n1);
-        load_ext(it.start + min(base + (int)threadIdx.x + 2 * kDepBlock, last), ne);
-        batch(base + threadIdx.x, r0, r1, re);
-        r0 = q0;
-        r1 = q1;
-        re = qe;
-        q0 = n0;
-        q1 = n1;
-        qe = ne;
+    if constexpr (kOrdered) {
+        // Wave w takes the pools (k * waves + w) of kPool records, k = 0, 1, ...; pool k + 1 is
+        // ordered (order_pool; its keys were issued a pool ago) and pool k + 2's keys are issued
+        // before pool k deposits, and every batch is loaded by index two batches ahead.  The
+        // loop starts at an empty pool -1 (dead lanes) so that it is entered with the loads in
+        // the order every iteration leaves them in -- keys, then records: the waits for the keys
+        // and before each batch stay counted vmcnt that leave the later loads in flight (keys
+        // issued last in a prologue, or pool -1 peeled off, made them vmcnt(0)).
+        OrderLds& ol = order_lds[threadIdx.x >> 6];
+        constexpr int kWaves = kDepBlock / 64;
+        auto pstart = [&](int k) { return (max(k, 0) * kWaves + (int)(threadIdx.x >> 6)) * kPool; };
+        auto pcount = [&](int k) { return k < 0 ? 0 : max(0, min(kPool, it.count - pstart(k))); };
+        auto load_keys = [&](int k, unsigned (&key)[kPoolBatches]) {  // the packed box words
+#pragma unroll
+            for (int j = 0; j < kPoolBatches; ++j)
+                key[j] = __float_as_uint(
+                    ((const float*)recs)[(it.start + min(pstart(k) + j * 64 + lane, last)) * 8 + 7]);
+        };
+        unsigned key[kPoolBatches];
+        load_keys(0, key);
+        asm volatile("" ::: "memory");  // keys first
+        load_rec(recs, it.start + min(pstart(0), last), r0, r1);
+        load_ext(it.start + min(pstart(0), last), re);
+        load_rec(recs, it.start + min(pstart(0) + 1, last), q0, q1);
+        load_ext(it.start + min(pstart(0) + 1, last), qe);
+        unsigned cidx = 0u;
+#pragma nounroll
+        for (int k = -1; k * (kWaves * kPool) < it.count; ++k) {
+            const int n = pcount(k), nn = pcount(k + 1);
+            const unsigned nidx = nn > 0 ? order_pool(key, nn, ol, lane) : 0u;
+            load_keys(k + 2, key);
+#pragma unroll
+            for (int j = 0; j < kPoolBatches; ++j) {
+                constexpr int kAhead = 2;  // batches
+                const int ni = j + kAhead < kPoolBatches
+                    ? pstart(k) + (int)(cidx >> (8 * ((j + kAhead) % kPoolBatches)) & 255u)
+                    : pstart(k + 1) + (int)(nidx >> (8 * ((j + kAhead) % kPoolBatches)) & 255u);
+                float4 n0, n1, ne;
+                load_rec(recs, it.start + min(ni, last), n0, n1);
+                load_ext(it.start + min(ni, last), ne);
+                // (positions past the pool's end are dead lanes: index it.count)
+                batch(j * 64 + lane < n ? pstart(k) + (int)(cidx >> (8 * j) & 255u) : it.count, r0, r1,
+                      re);
+                r0 = q0;
+                r1 = q1;
+                re = qe;
+                q0 = n0;
+                q1 = n1;
+                qe = ne;
+            }
+            cidx = nidx;
+        }
+        static_assert(kPoolBatches >= 2, "a batch is loaded two batches ahead: at most one pool");
+    } else {
+        load_rec(recs, it.start + min((int)threadIdx.x, last), r0, r1);
+        load_ext(it.start + min((int)threadIdx.x, last), re);
+        load_rec(recs, it.start + min((int)threadIdx.x + kDepBlock, last), q0, q1);
+        load_ext(it.start + min((int)threadIdx.x + kDepBlock, last), qe);
+        for (int base = 0; base < it.count; base += kDepBlock) {
+            float4 n0, n1, ne;
+            load_rec(recs, it.start + min(base + (int)threadIdx.x + 2 * kDepBlock, last), n0, n1);
+            load_ext(it.start + min(base + (int)threadIdx.x + 2 * kDepBlock, last), ne);
+            batch(base + threadIdx.x, r0, r1, re);
+            r0 = q0;
+            r1 = q1;
+            re = qe;
+            q0 = n0;
+            q1 = n1;
+            qe = ne;
+        }
     }
     if (ndef > 0)
         deferred<KID, NOUT, ACC, EXT>(g, s, recs, ext, pass, it.start, dlist, 0, ndef, X0, Y0, kk,
