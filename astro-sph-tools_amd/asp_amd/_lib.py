@@ -44,7 +44,11 @@ EXPORTS = ("asp_version", "asp_last_error", "asp_device_count", "asp_project2d",
            "asp_project3d", "asp_kernel_eval", "asp_chunk_ranges", "asp_pixel_neighbours", "asp_ratio",
            "asp_profile", "asp_profile_stages", "asp_profile_read", "asp_last_stats",
            "asp_release", "asp_stage_particles", "asp_periodic", "asp_wrapped_distance",
-           "asp_knn_smoothing_lengths", "asp_table_interp3", "asp_table_interp", "asp_nearest")
+           "asp_knn_smoothing_lengths", "asp_table_interp3", "asp_table_interp", "asp_nearest",
+           "asp_match_ids", "asp_take_rows")
+
+ASP_MATCH_MAPPING = 0
+ASP_MATCH_REORDER = 1
 
 STAGES = ("memset", "count", "colscan", "tilescan", "scatter", "scale", "deposit", "merge",
           "wide", "ratio", "cube_count", "cube_colscan", "cube_tilescan", "cube_scatter",
@@ -57,6 +61,7 @@ _f = C.POINTER(C.c_float)
 _d = C.POINTER(C.c_double)
 _i32 = C.POINTER(C.c_int32)
 _i64 = C.POINTER(C.c_int64)
+_u8 = C.POINTER(C.c_uint8)
 
 
 class ASPError(RuntimeError):
@@ -156,7 +161,11 @@ def lib():
                                     C.c_int32, C.c_int32, _d, _d, _d, C.c_int32, C.c_void_p])
     L.asp_nearest.argtypes = [_d, C.c_int64, _d, C.c_int64, C.POINTER(C.c_uint32), C.c_int32,
                               C.c_double, _i32, _d, C.c_int32, C.c_int32, C.c_void_p]
-    for name in ("asp_nearest", "asp_project2d", "asp_project2d_f64", "asp_pairs_begin", "asp_pairs_emit",
+    L.asp_match_ids.argtypes = [_i64, _u8, C.c_int64, _i64, _u8, C.c_int64, C.c_int32, _i32, _u8,
+                                _i64, C.c_int32, C.c_int32, C.c_void_p]
+    L.asp_take_rows.argtypes = [C.c_void_p, C.c_int64, C.c_int64, _i32, C.c_int64, C.c_void_p,
+                                C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    for name in ("asp_match_ids", "asp_take_rows", "asp_nearest", "asp_project2d", "asp_project2d_f64", "asp_pairs_begin", "asp_pairs_emit",
                  "asp_pairs_end", "asp_project3d", "asp_kernel_eval", "asp_chunk_ranges",
                  "asp_pixel_neighbours", "asp_ratio", "asp_profile", "asp_profile_stages",
                  "asp_profile_read", "asp_last_stats", "asp_release", "asp_stage_particles",

@@ -108,6 +108,9 @@ struct Workspace {
     // starts, entries, scan scratch, the ASP_NEAREST_COUNT counter, staged queries, staged
     // outputs, query sort keys, indices and scratch
     Buf nearest[13];
+    // asp_match_ids / asp_take_rows: staged IDs, filters, outputs; partition counts / cursors,
+    // starts; record keys, record positions; counters; scan scratch; staged rows, output, index
+    Buf match[12];
     Buf in[5], out[2], hist, cmx, tile_total, tile_start, tile_k, items, merges, counters, recs,
         wide, slabs, morton, aux[6], iorder;
     Buf in64[4];     // asp_project2d_f64: the caller's fp64 arrays, resident for exact decisions
@@ -146,6 +149,7 @@ struct Workspace {
         for (auto& b : aux) v.push_back(&b);
         for (auto& b : knn) v.push_back(&b);
         for (auto& b : nearest) v.push_back(&b);
+        for (auto& b : match) v.push_back(&b);
         for (auto& b : in64) v.push_back(&b);
         for (auto& b : pairs) v.push_back(&b);
         for (auto& b : inw) v.push_back(&b);

@@ -384,6 +384,66 @@ int asp_nearest(const double *positions, int64_t n, const double *centres, int64
                 double *distance, int32_t flags, int32_t device, void *stream);
 
 /*
+ * Cross-snapshot ID matching: the numerical core of tools/_ArrayReorder.py -- ArrayReorder
+ * (:815-1038) and ArrayMapping (:1042-1171), which line two ID orderings up with argsort /
+ * isin / searchsorted over int64 IDs (:1003-1038, :1057-1081).  For source IDs S with the
+ * optional filter sf and target IDs T with the optional filter tf (filters: one 0/1 byte
+ * per ID, NumPy bool_; NULL = all true):
+ *   index[j]          = the i with sf[i], tf[j] and S[i] == T[j]; -1 where there is none;
+ *   source_matched[i] = sf[i] and some j with tf[j] has T[j] == S[i]   (may be NULL);
+ *   counts[0] = targets with index >= 0, counts[1] = sources matched, counts[2] = duplicates
+ *   seen (0 = none).  A duplicate is an ID value carried by >= 2 filtered sources AND >= 1
+ *   filtered target: duplicated source IDs that no filtered target asks for, or that a
+ *   filter removes, are legal, and so are repeated targets (one-to-many).  With duplicates
+ *   the call still returns ASP_OK and index / source_matched are unspecified.
+ * IDs are arbitrary 64-bit patterns (uint64 IDs reinterpreted; no value is reserved).
+ * mode: which of the reference's two objects the caller builds -- it raises from the counts:
+ * ASP_MATCH_MAPPING an IndexError when counts[2] != 0 (:1074-1075), ASP_MATCH_REORDER a
+ * ValueError when counts[2] != 0 or counts[0] != counts[1] (:836-838: repeated targets make
+ * the two differ).  The outputs are the same in both modes.
+ * counts is ALWAYS a host array of 3 words and the call waits for it, as asp_nearest waits
+ * for its centre check; the other pointers are host pointers, staged through the device
+ * workspace, unless ASP_F_DEVICE_PTRS (device pointers, ordered on `stream`).
+ * ASP_ERR_INVALID before any device work, asp_last_error naming the condition: n_source < 0,
+ * n_target < 0, NULL arrays with non-zero sizes, NULL counts, a mode outside 0..1.  n_source
+ * or n_target >= 2^31: ASP_ERR_UNSUPPORTED (index is int32).  n_target == 0 is valid, needs
+ * no device and gives counts {0, 0, 0}; n_source == 0 is valid and gives every index -1.
+ * Method: a partitioned hash join; workspace 12 bytes per ID plus 16 bytes
+ * per partition.  Without duplicates index is unique, so the outputs are bit-reproducible.
+ * Environment (read per call): ASP_MATCH_CHUNK_KEYS = source keys per LDS round and the
+ * per-partition target (8..4096, rounded down to a power of two; default 4096, the tuned
+ * value; small values let tests reach many partitions and multi-round partitions at small
+ * n).  Results are identical for every value.  ASP_MATCH_STOP (diagnostic, for timing the
+ * phases from outside: 1 returns after the count and scans, 2 after the scatter; the outputs
+ * are then meaningless).
+ */
+#define ASP_MATCH_MAPPING 0 /* ArrayMapping: targets may repeat                             */
+#define ASP_MATCH_REORDER 1 /* ArrayReorder: also targets matched == sources matched        */
+int asp_match_ids(const int64_t *source_ids, const uint8_t *source_filter, int64_t n_source,
+                  const int64_t *target_ids, const uint8_t *target_filter, int64_t n_target,
+                  int32_t mode, int32_t *index, uint8_t *source_matched, int64_t *counts,
+                  int32_t flags, int32_t device, void *stream);
+
+/*
+ * The row gather that applies asp_match_ids' index: replaces the fancy-index copy per field
+ * of _ArrayReorder.py:957 and :1129.  data: n_rows rows of row_bytes bytes (any row_bytes
+ * >= 1: scalar fields, (N, 3) positions, int8 flags); out: n_index rows.
+ *   out[j] = data[index[j]]  for index[j] >= 0;
+ *   for index[j] < 0: fill_row (row_bytes bytes) -- or, with fill_row NULL, out[j] is left
+ *   untouched: the reference's call with an output_array and no default_value.
+ * An index >= n_rows is ASP_ERR_INVALID (found by the gather's own check, never
+ * dereferenced; out is then unspecified).  row_bytes < 1, negative sizes, NULL out / index
+ * with n_index > 0, NULL data with n_rows > 0: ASP_ERR_INVALID before any device work.
+ * Rows whose size and addresses are multiples of 16, 8 or 4 bytes move as vectors of that
+ * width, other rows byte by byte.  Host pointers unless ASP_F_DEVICE_PTRS (then every
+ * pointer, fill_row included, is a device pointer and the work is ordered on `stream`; the
+ * call waits for the index check).
+ */
+int asp_take_rows(const void *data, int64_t n_rows, int64_t row_bytes, const int32_t *index,
+                  int64_t n_index, const void *fill_row, void *out, int32_t flags,
+                  int32_t device, void *stream);
+
+/*
  * Ionisation-table interpolation: replaces the scipy
  * RegularGridInterpolator of data_structures/_IonisationTable.py:44-58 (linear,
  * bounds_error=False, fill_value=-inf; the HM01 tables of
