@@ -71,7 +71,7 @@ class ASPError(RuntimeError):
 def build():
     """Compile libasp_hip.so in-tree (hipcc --offload-arch=gfx950)."""
     import subprocess
-    subprocess.run(["make", "-s", "-C", ROOT], check=True)
+    subprocess.run(["make", "-s", "-j8", "-C", ROOT], check=True)
 
 
 def lib():

@@ -120,6 +120,21 @@ struct Merge {      // a tile split over several items: sum their slabs
     int pad;
 };
 
+// Counter words (int) shared by the pipeline stages.
+enum Ctr {
+    cItems = 0,     // work items (K2b)
+    cRecs = 1,      // records (K2b)
+    cWideCount = 2, // wide particles (K1)
+    cChunk = 3,     // records per item (K2b)
+    cWideCursor = 4,// wide list fill (K3)
+    cSlabs = 5,     // int64 partial slabs (K2b)
+    cMerges = 6,    // split tiles (K2b)
+    cWideMax0 = 7,  // max |c0| over wide particles, fp32 bits (K3)
+    cWideMax1 = 8,  // max |c1| over wide particles, fp32 bits (K3)
+    cLarge = 9,     // records in the large stream (K2b)
+    cNum = 16
+};
+
 __device__ __forceinline__ double corner_x(const Grid& g, int xi) {  // xi: window row
     return g.x_min + (double)(xi + g.ox) * g.psx;   // .pyx:13
 }

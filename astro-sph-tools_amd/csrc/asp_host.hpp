@@ -85,6 +85,52 @@ enum Stage {
     kSNearestPrep = 19, kSNearestSearch = 20
 };
 
+// What the slots of the workspace's buffer arrays hold (Workspace::knn, nearest, match,
+// aux, pairs).
+// asp_knn_smoothing_lengths
+enum KnnBuf {
+    kKnnPos, kKnnH,            // staged positions and smoothing lengths (host callers)
+    kKnnPartials,              // bounding-box reduction partials
+    kKnnKeys, kKnnIndex,       // sort keys and indices, in / out
+    kKnnSorted,                // positions in key order (SoA)
+    kKnnSortTmp,               // radix sort scratch
+    kKnnCells,                 // the level-L cell table
+    kKnnSubCells, kKnnSubTable,  // its sub-tables
+    kKnnBlockMin,              // the suffix-minimum block minima of the table's scan
+    kKnnCounters,              // the ASP_KNN_COUNT distance counters
+    kKnnBufCount
+};
+// asp_nearest
+enum NearestBuf {
+    kNearCentres, kNearMembers,  // staged centres and member words
+    kNearCheck,                  // check counters
+    kNearCellCount,              // cell counts, then cursors
+    kNearCellStart,
+    kNearEntries,
+    kNearScanTmp,                // scan scratch
+    kNearCounter,                // the ASP_NEAREST_COUNT counter
+    kNearQueries, kNearOutputs,  // staged queries and outputs
+    kNearSortKeys, kNearSortIndex, kNearSortTmp,  // the query sort
+    kNearestBufCount
+};
+// asp_match_ids / asp_take_rows
+enum MatchBuf {
+    kMatchIds, kMatchFilters, kMatchOutputs,  // staged IDs, filters, outputs
+    kMatchPartCount,                          // partition counts, then cursors
+    kMatchPartStart,
+    kMatchKeys, kMatchPositions,              // record keys and positions
+    kMatchCounters,           // asp_match_ids' counters; asp_take_rows' bad-index flag
+    kMatchScanTmp,            // scan scratch
+    kMatchRows, kMatchRowsOut, kMatchRowIndex,  // asp_take_rows: staged rows, output, index
+    kMatchBufCount
+};
+// Per-call scratch that several entry points reuse, each with its own meaning for slots
+// 0 .. 4 (a local enum at the top of the user); the last holds a call's few 64-bit
+// counter words (asp_stage_particles' image counts, the ASP_COUNT_EVALS sums).
+enum AuxBuf { kAuxCounters = 5, kAuxBufCount };
+// the kernel_func plug-in session: per-pixel pair counts, per-tile pair totals
+enum PairsBuf { kPairsPixCount, kPairsTileTotals, kPairsBufCount };
+
 struct Workspace {
     std::mutex mu;
     // HIP-event profiling (asp_profile): per-stage start/stop events of the last call,
@@ -100,23 +146,16 @@ struct Workspace {
     int pset = 0;                  // the set the current call records into
     double stage_ms[kStages] = {};
     long long stage_n[kStages] = {};
-    // asp_knn_smoothing_lengths (knn[7]: the level-L cell table, knn[8..9]: sub-tables,
-    // knn[10]: the suffix-minimum block minima of its scan, knn[11]: the ASP_KNN_COUNT
-    // distance counters)
-    Buf knn[12];
-    // asp_nearest: staged centres, member words, check counters, cell counts / cursors, cell
-    // starts, entries, scan scratch, the ASP_NEAREST_COUNT counter, staged queries, staged
-    // outputs, query sort keys, indices and scratch
-    Buf nearest[13];
-    // asp_match_ids / asp_take_rows: staged IDs, filters, outputs; partition counts / cursors,
-    // starts; record keys, record positions; counters; scan scratch; staged rows, output, index
-    Buf match[12];
+    Buf knn[kKnnBufCount];
+    Buf nearest[kNearestBufCount];
+    Buf match[kMatchBufCount];
+    Buf aux[kAuxBufCount];
     Buf in[5], out[2], hist, cmx, tile_total, tile_start, tile_k, items, merges, counters, recs,
-        wide, slabs, morton, aux[6], iorder;
+        wide, slabs, morton, iorder;
     Buf in64[4];     // asp_project2d_f64: the caller's fp64 arrays, resident for exact decisions
     Buf ext;         // asp_project2d_props: per record, the coefficients of properties 2..5
     Buf inx[4];      // asp_project2d_props_f64: fp32 working copies of properties 2..5
-    Buf pairs[4];    // asp_pair_list
+    Buf pairs[kPairsBufCount];  // the kernel_func plug-in session
     Buf inw[2];      // asp_project2d_sph(_f64) from host arrays: the masses and densities
     Buf wts[6];      // asp_project2d_sph(_f64): fp32 working copies of m / rho * property
     int* h_counters = nullptr;  // pinned

@@ -1202,24 +1202,24 @@ static int knn(const double* pos, long long n, int k, double* h, int flags, int 
     const double* dpos = pos;
     double* dh = h;
     if (!dev) {
-        ASP_TRY(ensure(ws.knn[0], (size_t)n * 3 * sizeof(double)));
-        ASP_TRY(ensure(ws.knn[1], (size_t)n * sizeof(double)));
-        ASP_HIP(hipMemcpyAsync(ws.knn[0].p, pos, (size_t)n * 3 * sizeof(double),
+        ASP_TRY(ensure(ws.knn[kKnnPos], (size_t)n * 3 * sizeof(double)));
+        ASP_TRY(ensure(ws.knn[kKnnH], (size_t)n * sizeof(double)));
+        ASP_HIP(hipMemcpyAsync(ws.knn[kKnnPos].p, pos, (size_t)n * 3 * sizeof(double),
                                hipMemcpyHostToDevice, st));
-        dpos = (const double*)ws.knn[0].p;
-        dh = (double*)ws.knn[1].p;
+        dpos = (const double*)ws.knn[kKnnPos].p;
+        dh = (double*)ws.knn[kKnnH].p;
     }
-    ASP_TRY(ensure(ws.knn[2], (size_t)kRedBlocks * 6 * sizeof(double) + 256));
-    ASP_TRY(ensure(ws.knn[3], (size_t)n * 2 * sizeof(unsigned long long)));  // keys in / out
-    ASP_TRY(ensure(ws.knn[4], (size_t)n * 2 * sizeof(int)));                 // index in / out
-    ASP_TRY(ensure(ws.knn[5], (size_t)n * 3 * sizeof(double)));              // sorted SoA
-    double* part = (double*)ws.knn[2].p;
+    ASP_TRY(ensure(ws.knn[kKnnPartials], (size_t)kRedBlocks * 6 * sizeof(double) + 256));
+    ASP_TRY(ensure(ws.knn[kKnnKeys], (size_t)n * 2 * sizeof(unsigned long long)));  // keys in / out
+    ASP_TRY(ensure(ws.knn[kKnnIndex], (size_t)n * 2 * sizeof(int)));                 // index in / out
+    ASP_TRY(ensure(ws.knn[kKnnSorted], (size_t)n * 3 * sizeof(double)));              // sorted SoA
+    double* part = (double*)ws.knn[kKnnPartials].p;
     KGrid* dg = (KGrid*)(part + kRedBlocks * 6);
-    unsigned long long* kin = (unsigned long long*)ws.knn[3].p;
+    unsigned long long* kin = (unsigned long long*)ws.knn[kKnnKeys].p;
     unsigned long long* kout = kin + n;
-    int* iin = (int*)ws.knn[4].p;
+    int* iin = (int*)ws.knn[kKnnIndex].p;
     int* iout = iin + n;
-    double* xs = (double*)ws.knn[5].p;
+    double* xs = (double*)ws.knn[kKnnSorted].p;
     double *ys = xs + n, *zs = ys + n;
     const unsigned nb = (unsigned)std::min<long long>(kRedBlocks, (n + kKnnBlock - 1) / kKnnBlock);
     const unsigned grid = (unsigned)((n + kKnnBlock - 1) / kKnnBlock);
@@ -1235,8 +1235,8 @@ static int knn(const double* pos, long long n, int k, double* h, int flags, int 
     size_t tmp = 0;
     ASP_HIP(rocprim::radix_sort_pairs(nullptr, tmp, kin, kout, iin, iout, (size_t)n, 0, 3 * kQBits,
                                       st));
-    ASP_TRY(ensure(ws.knn[6], tmp));
-    ASP_HIP(rocprim::radix_sort_pairs(ws.knn[6].p, tmp, kin, kout, iin, iout, (size_t)n, 0,
+    ASP_TRY(ensure(ws.knn[kKnnSortTmp], tmp));
+    ASP_HIP(rocprim::radix_sort_pairs(ws.knn[kKnnSortTmp].p, tmp, kin, kout, iin, iout, (size_t)n, 0,
                                       3 * kQBits, st));
     hipLaunchKernelGGL(k_gather, dim3(grid), dim3(kKnnBlock), 0, st, dpos, (long long)n,
                        (const int*)iout, xs, ys, zs);
@@ -1245,8 +1245,8 @@ static int knn(const double* pos, long long n, int k, double* h, int flags, int 
     int L = 1;
     while (L < 9 && (1LL << (3 * L)) < n) ++L;
     const long long ncell = 1LL << (3 * L);
-    ASP_TRY(ensure(ws.knn[7], (size_t)(ncell + 1) * sizeof(int)));
-    int* tab = (int*)ws.knn[7].p;
+    ASP_TRY(ensure(ws.knn[kKnnCells], (size_t)(ncell + 1) * sizeof(int)));
+    int* tab = (int*)ws.knn[kKnnCells].p;
     ASP_HIP(hipMemsetD32Async((hipDeviceptr_t)tab, (int)n, (size_t)(ncell + 1), st));
     hipLaunchKernelGGL(k_cell_starts, dim3(grid), dim3(kKnnBlock), 0, st,
                        (const unsigned long long*)kout, (long long)n, kKeyBits - 3 * L, tab);
@@ -1254,8 +1254,8 @@ static int knn(const double* pos, long long n, int k, double* h, int flags, int 
     {  // the empty cells: suffix minimum over the ncell + 1 entries
         const long long m = ncell + 1;
         const int nbs = (int)((m + kSfxSpan - 1) / kSfxSpan);
-        ASP_TRY(ensure(ws.knn[10], (size_t)nbs * sizeof(int)));
-        int* bmin = (int*)ws.knn[10].p;
+        ASP_TRY(ensure(ws.knn[kKnnBlockMin], (size_t)nbs * sizeof(int)));
+        int* bmin = (int*)ws.knn[kKnnBlockMin].p;
         hipLaunchKernelGGL(k_sfx_block, dim3(nbs), dim3(kSfxBlock), 0, st, tab, m, bmin);
         ASP_LAUNCHED();
         hipLaunchKernelGGL(k_sfx_top, dim3(1), dim3(kSfxBlock), 0, st, bmin, nbs);
@@ -1267,11 +1267,11 @@ static int knn(const double* pos, long long n, int k, double* h, int flags, int 
     // sub-tables of the dense level-L cells: at most n / (kSubMin + 1) of them
     const int submin = (int)env_int("ASP_KNN_SUBMIN", kSubMin, 8);
     const long long nslot_max = n / (submin + 1) + 1;
-    ASP_TRY(ensure(ws.knn[8], (size_t)(ncell + 1) * sizeof(int)));
-    ASP_TRY(ensure(ws.knn[9], (size_t)nslot_max * (kSubCells + 1) * sizeof(int)));
-    int* sub = (int*)ws.knn[8].p;
+    ASP_TRY(ensure(ws.knn[kKnnSubCells], (size_t)(ncell + 1) * sizeof(int)));
+    ASP_TRY(ensure(ws.knn[kKnnSubTable], (size_t)nslot_max * (kSubCells + 1) * sizeof(int)));
+    int* sub = (int*)ws.knn[kKnnSubCells].p;
     int* nslot = sub + ncell;
-    int* subtab = (int*)ws.knn[9].p;
+    int* subtab = (int*)ws.knn[kKnnSubTable].p;
     ASP_HIP(hipMemsetAsync(nslot, 0, sizeof(int), st));
     hipLaunchKernelGGL(k_sub_slots, dim3((unsigned)((ncell + kKnnBlock - 1) / kKnnBlock)),
                        dim3(kKnnBlock), 0, st, (const int*)tab, ncell, submin, sub, nslot);
@@ -1303,8 +1303,8 @@ static int knn(const double* pos, long long n, int k, double* h, int flags, int 
     // [11] entries the shared cell pass streamed (once per wave), [12] top-k insertions
     unsigned long long* evc = nullptr;
     if (env_set("ASP_KNN_COUNT")) {
-        ASP_TRY(ensure(ws.knn[11], 8 * sizeof(unsigned long long)));
-        evc = (unsigned long long*)ws.knn[11].p;
+        ASP_TRY(ensure(ws.knn[kKnnCounters], 8 * sizeof(unsigned long long)));
+        evc = (unsigned long long*)ws.knn[kKnnCounters].p;
         ASP_HIP(hipMemsetAsync(evc, 0, 8 * sizeof(unsigned long long), st));
     }
     StageMark msearch(ws, kSKnnSearch, st);

@@ -278,11 +278,11 @@ static int match_ids(const long long* S, const unsigned char* sf, long long ns, 
     unsigned char* dmatched = source_matched;
     if (!dev) {
         const size_t in_bytes = (size_t)(ns + nt) * 8;
-        ASP_TRY(ensure(ws.match[0], in_bytes));
-        ASP_TRY(ensure(ws.match[1], (size_t)(ns + nt)));
-        ASP_TRY(ensure(ws.match[2], (size_t)nt * 4 + (size_t)ns));
-        long long* d_ids = (long long*)ws.match[0].p;
-        unsigned char* d_f = (unsigned char*)ws.match[1].p;
+        ASP_TRY(ensure(ws.match[kMatchIds], in_bytes));
+        ASP_TRY(ensure(ws.match[kMatchFilters], (size_t)(ns + nt)));
+        ASP_TRY(ensure(ws.match[kMatchOutputs], (size_t)nt * 4 + (size_t)ns));
+        long long* d_ids = (long long*)ws.match[kMatchIds].p;
+        unsigned char* d_f = (unsigned char*)ws.match[kMatchFilters].p;
         ASP_HIP(hipMemcpyAsync(d_ids, S, (size_t)ns * 8, hipMemcpyHostToDevice, st));
         ASP_HIP(hipMemcpyAsync(d_ids + ns, T, (size_t)nt * 8, hipMemcpyHostToDevice, st));
         dS = d_ids;
@@ -295,25 +295,26 @@ static int match_ids(const long long* S, const unsigned char* sf, long long ns, 
             ASP_HIP(hipMemcpyAsync(d_f + ns, tf, (size_t)nt, hipMemcpyHostToDevice, st));
             dtf = d_f + ns;
         }
-        dindex = (int*)ws.match[2].p;
-        dmatched = source_matched ? (unsigned char*)ws.match[2].p + (size_t)nt * 4 : nullptr;
+        dindex = (int*)ws.match[kMatchOutputs].p;
+        dmatched = source_matched ? (unsigned char*)ws.match[kMatchOutputs].p + (size_t)nt * 4
+                                  : nullptr;
     }
 
     // ---- workspace: 2 x (P + 1) counts, 2 x (P + 1) starts, records (12 B per ID) ----
-    ASP_TRY(ensure(ws.match[3], (size_t)(P + 1) * 2 * sizeof(int)));
-    ASP_TRY(ensure(ws.match[4], (size_t)(P + 1) * 2 * sizeof(int)));
-    ASP_TRY(ensure(ws.match[5], (size_t)(ns + nt) * 8));
-    ASP_TRY(ensure(ws.match[6], (size_t)(ns + nt) * 4));
-    ASP_TRY(ensure(ws.match[7], 4 * sizeof(unsigned long long)));
-    int* scnt = (int*)ws.match[3].p;
+    ASP_TRY(ensure(ws.match[kMatchPartCount], (size_t)(P + 1) * 2 * sizeof(int)));
+    ASP_TRY(ensure(ws.match[kMatchPartStart], (size_t)(P + 1) * 2 * sizeof(int)));
+    ASP_TRY(ensure(ws.match[kMatchKeys], (size_t)(ns + nt) * 8));
+    ASP_TRY(ensure(ws.match[kMatchPositions], (size_t)(ns + nt) * 4));
+    ASP_TRY(ensure(ws.match[kMatchCounters], 4 * sizeof(unsigned long long)));
+    int* scnt = (int*)ws.match[kMatchPartCount].p;
     int* tcnt = scnt + (P + 1);
-    int* sstart = (int*)ws.match[4].p;
+    int* sstart = (int*)ws.match[kMatchPartStart].p;
     int* tstart = sstart + (P + 1);
-    long long* skey = (long long*)ws.match[5].p;
+    long long* skey = (long long*)ws.match[kMatchKeys].p;
     long long* tkey = skey + ns;
-    int* sidx = (int*)ws.match[6].p;
+    int* sidx = (int*)ws.match[kMatchPositions].p;
     int* tidx = sidx + ns;
-    unsigned long long* ctr = (unsigned long long*)ws.match[7].p;
+    unsigned long long* ctr = (unsigned long long*)ws.match[kMatchCounters].p;
     // the counters after the join, plus [3]: records per side (filtered IDs) are the scans' ends
     ASP_HIP(hipMemsetAsync(scnt, 0, (size_t)(P + 1) * 2 * sizeof(int), st));
     ASP_HIP(hipMemsetAsync(ctr, 0, 4 * sizeof(unsigned long long), st));
@@ -328,10 +329,10 @@ static int match_ids(const long long* S, const unsigned char* sf, long long ns, 
     size_t tmp = 0;
     ASP_HIP(rocprim::exclusive_scan(nullptr, tmp, scnt, sstart, 0, (size_t)(P + 1),
                                     rocprim::plus<int>(), st));
-    ASP_TRY(ensure(ws.match[8], tmp));
-    ASP_HIP(rocprim::exclusive_scan(ws.match[8].p, tmp, scnt, sstart, 0, (size_t)(P + 1),
+    ASP_TRY(ensure(ws.match[kMatchScanTmp], tmp));
+    ASP_HIP(rocprim::exclusive_scan(ws.match[kMatchScanTmp].p, tmp, scnt, sstart, 0, (size_t)(P + 1),
                                     rocprim::plus<int>(), st));
-    ASP_HIP(rocprim::exclusive_scan(ws.match[8].p, tmp, tcnt, tstart, 0, (size_t)(P + 1),
+    ASP_HIP(rocprim::exclusive_scan(ws.match[kMatchScanTmp].p, tmp, tcnt, tstart, 0, (size_t)(P + 1),
                                     rocprim::plus<int>(), st));
     ASP_HIP(hipMemsetAsync(scnt, 0, (size_t)(P + 1) * 2 * sizeof(int), st));  // now the cursors
     if (stop >= 2) {
@@ -449,26 +450,28 @@ static int take_rows(const void* data, long long n_rows, long long row_bytes, co
     const size_t out_bytes = (size_t)n_index * (size_t)row_bytes;
     if (!dev) {
         const size_t rb16 = ((size_t)row_bytes + 15) / 16 * 16;
-        ASP_TRY(ensure(ws.match[9], (size_t)n_rows * (size_t)row_bytes));
-        ASP_TRY(ensure(ws.match[10], out_bytes + rb16));
-        ASP_TRY(ensure(ws.match[11], (size_t)n_index * 4));
+        ASP_TRY(ensure(ws.match[kMatchRows], (size_t)n_rows * (size_t)row_bytes));
+        ASP_TRY(ensure(ws.match[kMatchRowsOut], out_bytes + rb16));
+        ASP_TRY(ensure(ws.match[kMatchRowIndex], (size_t)n_index * 4));
         if (n_rows > 0)
-            ASP_HIP(hipMemcpyAsync(ws.match[9].p, data, (size_t)n_rows * (size_t)row_bytes,
+            ASP_HIP(hipMemcpyAsync(ws.match[kMatchRows].p, data, (size_t)n_rows * (size_t)row_bytes,
                                    hipMemcpyHostToDevice, st));
-        ASP_HIP(hipMemcpyAsync(ws.match[11].p, index, (size_t)n_index * 4, hipMemcpyHostToDevice, st));
-        ddata = ws.match[9].p;
-        dindex = (const int*)ws.match[11].p;
+        ASP_HIP(hipMemcpyAsync(ws.match[kMatchRowIndex].p, index, (size_t)n_index * 4,
+                               hipMemcpyHostToDevice, st));
+        ddata = ws.match[kMatchRows].p;
+        dindex = (const int*)ws.match[kMatchRowIndex].p;
         // the fill row first (16-byte slot), then the output
-        dout = (unsigned char*)ws.match[10].p + rb16;
+        dout = (unsigned char*)ws.match[kMatchRowsOut].p + rb16;
         if (fill) {
-            ASP_HIP(hipMemcpyAsync(ws.match[10].p, fill, (size_t)row_bytes, hipMemcpyHostToDevice, st));
-            dfill = ws.match[10].p;
+            ASP_HIP(hipMemcpyAsync(ws.match[kMatchRowsOut].p, fill, (size_t)row_bytes,
+                                   hipMemcpyHostToDevice, st));
+            dfill = ws.match[kMatchRowsOut].p;
         } else {  // unmatched rows keep the caller's bytes
             ASP_HIP(hipMemcpyAsync(dout, out, out_bytes, hipMemcpyHostToDevice, st));
         }
     }
-    ASP_TRY(ensure(ws.match[7], 4 * sizeof(unsigned long long)));
-    int* bad = (int*)ws.match[7].p;
+    ASP_TRY(ensure(ws.match[kMatchCounters], 4 * sizeof(unsigned long long)));
+    int* bad = (int*)ws.match[kMatchCounters].p;
     ASP_HIP(hipMemsetAsync(bad, 0, sizeof(int), st));
     // the widest unit that divides the row and that every pointer is aligned to
     const uintptr_t al = (uintptr_t)ddata | (uintptr_t)dout | (uintptr_t)dfill | (uintptr_t)row_bytes;

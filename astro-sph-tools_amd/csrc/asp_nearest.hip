@@ -373,22 +373,22 @@ static int nearest(const double* pos, long long n, const double* centres, long l
     const double* dc = centres;
     const unsigned* dm = member;
     if (!dev && m > 0) {
-        ASP_TRY(ensure(ws.nearest[0], (size_t)m * 3 * sizeof(double)));
-        ASP_HIP(hipMemcpyAsync(ws.nearest[0].p, centres, (size_t)m * 3 * sizeof(double),
+        ASP_TRY(ensure(ws.nearest[kNearCentres], (size_t)m * 3 * sizeof(double)));
+        ASP_HIP(hipMemcpyAsync(ws.nearest[kNearCentres].p, centres, (size_t)m * 3 * sizeof(double),
                                hipMemcpyHostToDevice, st));
-        dc = (const double*)ws.nearest[0].p;
+        dc = (const double*)ws.nearest[kNearCentres].p;
         if (member) {
-            ASP_TRY(ensure(ws.nearest[1], (size_t)m * sizeof(unsigned)));
-            ASP_HIP(hipMemcpyAsync(ws.nearest[1].p, member, (size_t)m * sizeof(unsigned),
+            ASP_TRY(ensure(ws.nearest[kNearMembers], (size_t)m * sizeof(unsigned)));
+            ASP_HIP(hipMemcpyAsync(ws.nearest[kNearMembers].p, member, (size_t)m * sizeof(unsigned),
                                    hipMemcpyHostToDevice, st));
-            dm = (const unsigned*)ws.nearest[1].p;
+            dm = (const unsigned*)ws.nearest[kNearMembers].p;
         }
     }
     const unsigned cgrid = (unsigned)((m + kNBlock - 1) / kNBlock);
     int h[1 + kMaxSets] = {0};
     if (m > 0) {
-        ASP_TRY(ensure(ws.nearest[2], sizeof(h)));
-        int* dcnt = (int*)ws.nearest[2].p;
+        ASP_TRY(ensure(ws.nearest[kNearCheck], sizeof(h)));
+        int* dcnt = (int*)ws.nearest[kNearCheck].p;
         ASP_HIP(hipMemsetAsync(dcnt, 0, sizeof(h), st));
         hipLaunchKernelGGL(k_ncheck, dim3(cgrid), dim3(kNBlock), 0, st, dc, (long long)m, dm, nsets,
                            L, dcnt);
@@ -426,12 +426,13 @@ static int nearest(const double* pos, long long n, const double* centres, long l
         if (nent > 0x7fffffffLL)
             return fail(ASP_ERR_UNSUPPORTED, ">= 2^31 set members over all sets");
     }
-    ASP_TRY(ensure(ws.nearest[3], (size_t)(ncell + 1) * sizeof(int)));  // counts, then cursors
-    ASP_TRY(ensure(ws.nearest[4], (size_t)(ncell + 1) * sizeof(int)));  // cell starts
-    ASP_TRY(ensure(ws.nearest[5], (size_t)nent * sizeof(NEnt)));
-    int* cnt = (int*)ws.nearest[3].p;
-    int* start = (int*)ws.nearest[4].p;
-    NEnt* ent = (NEnt*)ws.nearest[5].p;
+    // (counts, then cursors)
+    ASP_TRY(ensure(ws.nearest[kNearCellCount], (size_t)(ncell + 1) * sizeof(int)));
+    ASP_TRY(ensure(ws.nearest[kNearCellStart], (size_t)(ncell + 1) * sizeof(int)));  // cell starts
+    ASP_TRY(ensure(ws.nearest[kNearEntries], (size_t)nent * sizeof(NEnt)));
+    int* cnt = (int*)ws.nearest[kNearCellCount].p;
+    int* start = (int*)ws.nearest[kNearCellStart].p;
+    NEnt* ent = (NEnt*)ws.nearest[kNearEntries].p;
     if (nent > 0) {
         ASP_HIP(hipMemsetAsync(cnt, 0, (size_t)(ncell + 1) * sizeof(int), st));
         hipLaunchKernelGGL(k_ncount, dim3(cgrid), dim3(kNBlock), 0, st, dc, (long long)m, dm, nsets, T,
@@ -440,9 +441,9 @@ static int nearest(const double* pos, long long n, const double* centres, long l
         size_t tmp = 0;
         ASP_HIP(rocprim::exclusive_scan(nullptr, tmp, cnt, start, 0, (size_t)(ncell + 1),
                                         rocprim::plus<int>(), st));
-        ASP_TRY(ensure(ws.nearest[6], tmp));
-        ASP_HIP(rocprim::exclusive_scan(ws.nearest[6].p, tmp, cnt, start, 0, (size_t)(ncell + 1),
-                                        rocprim::plus<int>(), st));
+        ASP_TRY(ensure(ws.nearest[kNearScanTmp], tmp));
+        ASP_HIP(rocprim::exclusive_scan(ws.nearest[kNearScanTmp].p, tmp, cnt, start, 0,
+                                        (size_t)(ncell + 1), rocprim::plus<int>(), st));
         ASP_HIP(hipMemsetAsync(cnt, 0, (size_t)(ncell + 1) * sizeof(int), st));
         hipLaunchKernelGGL(k_nfill, dim3(cgrid), dim3(kNBlock), 0, st, dc, (long long)m, dm, nsets, T,
                            (const int*)start, cnt, ent);
@@ -455,8 +456,8 @@ static int nearest(const double* pos, long long n, const double* centres, long l
     // runs) -> asp_last_stats[9]
     unsigned long long* evc = nullptr;
     if (env_set("ASP_NEAREST_COUNT")) {
-        ASP_TRY(ensure(ws.nearest[7], sizeof(unsigned long long)));
-        evc = (unsigned long long*)ws.nearest[7].p;
+        ASP_TRY(ensure(ws.nearest[kNearCounter], sizeof(unsigned long long)));
+        evc = (unsigned long long*)ws.nearest[kNearCounter].p;
         ASP_HIP(hipMemsetAsync(evc, 0, sizeof(unsigned long long), st));
     }
     // ASP_NEAREST_SORT (read per call, so one process can time both): 1 = the queries of a
@@ -466,19 +467,20 @@ static int nearest(const double* pos, long long n, const double* centres, long l
     const int prune = env_int("ASP_NEAREST_PRUNE", 1) != 0;
     const long long B = std::min(n, (long long)env_int("ASP_NEAREST_BATCH", kNBatch, 1, kNBatch));
     if (!dev) {
-        ASP_TRY(ensure(ws.nearest[8], (size_t)B * 3 * sizeof(double)));
-        ASP_TRY(ensure(ws.nearest[9], (size_t)B * nsets * (sizeof(double) + sizeof(int))));
+        ASP_TRY(ensure(ws.nearest[kNearQueries], (size_t)B * 3 * sizeof(double)));
+        ASP_TRY(ensure(ws.nearest[kNearOutputs],
+                       (size_t)B * nsets * (sizeof(double) + sizeof(int))));
     }
     unsigned *kin = nullptr, *kout = nullptr;
     int *iin = nullptr, *iout = nullptr;
     int key_bits = 3;
     while ((1 << (key_bits / 3)) < gmax) key_bits += 3;
     if (sorted) {
-        ASP_TRY(ensure(ws.nearest[10], (size_t)B * 2 * sizeof(unsigned)));
-        ASP_TRY(ensure(ws.nearest[11], (size_t)B * 2 * sizeof(int)));
-        kin = (unsigned*)ws.nearest[10].p;
+        ASP_TRY(ensure(ws.nearest[kNearSortKeys], (size_t)B * 2 * sizeof(unsigned)));
+        ASP_TRY(ensure(ws.nearest[kNearSortIndex], (size_t)B * 2 * sizeof(int)));
+        kin = (unsigned*)ws.nearest[kNearSortKeys].p;
         kout = kin + B;
-        iin = (int*)ws.nearest[11].p;
+        iin = (int*)ws.nearest[kNearSortIndex].p;
         iout = iin + B;
     }
     for (long long a = 0; a < n; a += B) {
@@ -489,10 +491,10 @@ static int nearest(const double* pos, long long n, const double* centres, long l
         double* ddist = distance + a;
         long long ostride = n;
         if (!dev) {
-            ASP_HIP(hipMemcpyAsync(ws.nearest[8].p, pos + 3 * a, (size_t)nb * 3 * sizeof(double),
-                                   hipMemcpyHostToDevice, st));
-            dpos = (const double*)ws.nearest[8].p;
-            ddist = (double*)ws.nearest[9].p;
+            ASP_HIP(hipMemcpyAsync(ws.nearest[kNearQueries].p, pos + 3 * a,
+                                   (size_t)nb * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+            dpos = (const double*)ws.nearest[kNearQueries].p;
+            ddist = (double*)ws.nearest[kNearOutputs].p;
             dindex = (int*)(ddist + (size_t)B * nsets);
             ostride = B;
         }
@@ -503,9 +505,9 @@ static int nearest(const double* pos, long long n, const double* centres, long l
             size_t tmp = 0;
             ASP_HIP(rocprim::radix_sort_pairs(nullptr, tmp, kin, kout, iin, iout, (size_t)nb, 0,
                                               key_bits, st));
-            ASP_TRY(ensure(ws.nearest[12], tmp));
-            ASP_HIP(rocprim::radix_sort_pairs(ws.nearest[12].p, tmp, kin, kout, iin, iout, (size_t)nb,
-                                              0, key_bits, st));
+            ASP_TRY(ensure(ws.nearest[kNearSortTmp], tmp));
+            ASP_HIP(rocprim::radix_sort_pairs(ws.nearest[kNearSortTmp].p, tmp, kin, kout, iin, iout,
+                                              (size_t)nb, 0, key_bits, st));
         }
         if (evc)
             hipLaunchKernelGGL(k_nearest<true>, dim3(grid), dim3(kNBlock), 0, st, dpos, nb,

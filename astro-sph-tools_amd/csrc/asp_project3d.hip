@@ -264,7 +264,7 @@ __device__ __forceinline__ Box3 rec_box(float bits_f) {
 // the union of theirs -- GRP x fewer (workgroup, brick) runs open at once (the scatter's
 // record stores cost with the number of open runs; 512 workgroups of 512
 // -> 256 of 1024: scatter 3.91 -> 3.62 ms at 10^8 / 512^3, count unchanged).
-template <int PROBE, int TB>  // PROBE 1: the placement trials' launches (asp_project2d.hip k_scatter)
+template <int PROBE, int TB>  // PROBE 1: the placement trials' launches (asp_map_bin.hip k_scatter)
 __global__ __launch_bounds__(TB) void k3_scatter(
     const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
     const float* __restrict__ h, const float* __restrict__ a, long long n, long long per_block,

@@ -241,8 +241,8 @@ static int stage_particles(const double* pos, const double* h, const double* a0,
     std::lock_guard<std::mutex> lock(ws.mu);
     ASP_TRY(ws_begin(ws, st));
     WsEnd ws_end_(ws, st);
-    ASP_TRY(ensure(ws.aux[5], 2 * sizeof(unsigned long long)));
-    unsigned long long* dimg = (unsigned long long*)ws.aux[5].p;
+    ASP_TRY(ensure(ws.aux[kAuxCounters], 2 * sizeof(unsigned long long)));
+    unsigned long long* dimg = (unsigned long long*)ws.aux[kAuxCounters].p;
     ASP_HIP(hipMemsetAsync(dimg, 0, 2 * sizeof(unsigned long long), st));
     if ((flags & ASP_F_DEVICE_PTRS) || n == 0) {
         if (n > 0) {
@@ -256,7 +256,9 @@ static int stage_particles(const double* pos, const double* h, const double* a0,
         // conversion of chunk c.
         ASP_TRY(ensure_side(ws));
         const long long C = std::min<long long>(kStageChunk, n);
-        for (int s = 0; s < 2; ++s) ASP_TRY(ensure(ws.aux[s], (size_t)C * 6 * sizeof(double)));
+        enum { kSet = 0 };  // per-call scratch: the two staging sets, aux[kSet + 0 / 1]
+        for (int s = 0; s < 2; ++s)
+            ASP_TRY(ensure(ws.aux[kSet + s], (size_t)C * 6 * sizeof(double)));
         hipStream_t ss[2] = {st, ws.side};
         ASP_HIP(hipEventRecord(ws.scan_ev, st));
         ASP_HIP(hipStreamWaitEvent(ws.side, ws.scan_ev, 0));  // behind the counter reset
@@ -264,7 +266,7 @@ static int stage_particles(const double* pos, const double* h, const double* a0,
         for (long long i0 = 0; i0 < n; i0 += C, ++c) {
             const long long m = std::min(C, n - i0);
             hipStream_t s = ss[c & 1];
-            double* d = (double*)ws.aux[c & 1].p;
+            double* d = (double*)ws.aux[kSet + (c & 1)].p;
             double *dp = d, *dh = d + 3 * C, *d0 = d + 4 * C, *d1 = d + 5 * C;
             ASP_TRY(h2d_staged(ws, dp, pos + 3 * i0, (size_t)m * 3 * sizeof(double), s));
             if (h) ASP_TRY(h2d_staged(ws, dh, h + i0, (size_t)m * sizeof(double), s));

@@ -2,7 +2,8 @@
 
 The reference tiles ANY image (_projector.py:88-107).  The device pipeline holds at most
 4096 GPU tiles of 64 x 64 pixels per pass, so larger images run as windows of whole tile
-rows (asp_project2d.hip ``window_grid``): pixel corners, pitches (including the y-pitch
+rows (``window_grid`` of the pass driver, asp_project2d.hip; the kernels it launches are in
+asp_map_bin.hip and asp_map_deposit.hip): pixel corners, pitches (including the y-pitch
 quirk S2, Δy = (y_max - y_min)/Nx) and the reference's chunk cull stay the whole image's.
 Particle counts beyond one pass (32-bit indices and record cursors) run as batches that
 accumulate into the same maps (``ASP_MAX_BATCH`` / ``ASP_MAX_RECORDS`` lower the limits
