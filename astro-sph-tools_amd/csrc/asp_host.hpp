@@ -52,6 +52,7 @@ inline bool env_set(const char* name) { return getenv(name) != nullptr; }
 // Runtime (kernel id, map count, deterministic) -> compile-time constants: calls
 // f(Int<KID>, Int<NOUT>, Int<ACC>) with ACC = 0 (fp64 sums) / 1 (fixed point), the values of
 // kAccF64 / kAccFix.  f is a generic lambda; only the combinations named here instantiate.
+// Used by the 2-D map's launchers (asp_map_bin.hip, asp_map_deposit.hip).
 template <int V>
 using Int = std::integral_constant<int, V>;
 template <class F>
@@ -131,7 +132,35 @@ enum AuxBuf { kAuxCounters = 5, kAuxBufCount };
 // the kernel_func plug-in session: per-pixel pair counts, per-tile pair totals
 enum PairsBuf { kPairsPixCount, kPairsTileTotals, kPairsBufCount };
 
-struct Workspace {
+// Every device buffer of a workspace, and nothing else: free_buffers walks the struct as
+// an array of Buf, so a buffer added here is released with the rest.
+struct WorkspaceBufs {
+    Buf knn[kKnnBufCount];
+    Buf nearest[kNearestBufCount];
+    Buf match[kMatchBufCount];
+    Buf aux[kAuxBufCount];
+    Buf in[5], out[2], hist, cmx, tile_total, tile_start, tile_k, items, merges, counters, recs,
+        wide, slabs, morton, iorder;
+    Buf morton3;     // brick order of the 3-D cube
+    Buf in64[4];     // asp_project2d_f64: the caller's fp64 arrays, resident for exact decisions
+    Buf ext;         // asp_project2d_props: per record, the coefficients of properties 2..5
+    Buf inx[4];      // asp_project2d_props_f64: fp32 working copies of properties 2..5
+    Buf pairs[kPairsBufCount];  // the kernel_func plug-in session
+    Buf inw[2];      // asp_project2d_sph(_f64) from host arrays: the masses and densities
+    Buf wts[6];      // asp_project2d_sph(_f64): fp32 working copies of m / rho * property
+};
+static_assert(std::is_standard_layout<WorkspaceBufs>::value, "viewed as an array of Buf");
+static_assert(sizeof(WorkspaceBufs) % sizeof(Buf) == 0, "Buf members only");
+
+inline void free_buffers(WorkspaceBufs& bufs) {
+    Buf* b = reinterpret_cast<Buf*>(&bufs);
+    for (size_t k = 0; k < sizeof(WorkspaceBufs) / sizeof(Buf); ++k) {
+        if (b[k].p) (void)hipFree(b[k].p);
+        b[k] = Buf{};
+    }
+}
+
+struct Workspace : WorkspaceBufs {
     std::mutex mu;
     // HIP-event profiling (asp_profile): per-stage start/stop events of the last call,
     // folded into the running sums at the next call or at asp_profile_read.
@@ -146,18 +175,6 @@ struct Workspace {
     int pset = 0;                  // the set the current call records into
     double stage_ms[kStages] = {};
     long long stage_n[kStages] = {};
-    Buf knn[kKnnBufCount];
-    Buf nearest[kNearestBufCount];
-    Buf match[kMatchBufCount];
-    Buf aux[kAuxBufCount];
-    Buf in[5], out[2], hist, cmx, tile_total, tile_start, tile_k, items, merges, counters, recs,
-        wide, slabs, morton, iorder;
-    Buf in64[4];     // asp_project2d_f64: the caller's fp64 arrays, resident for exact decisions
-    Buf ext;         // asp_project2d_props: per record, the coefficients of properties 2..5
-    Buf inx[4];      // asp_project2d_props_f64: fp32 working copies of properties 2..5
-    Buf pairs[kPairsBufCount];  // the kernel_func plug-in session
-    Buf inw[2];      // asp_project2d_sph(_f64) from host arrays: the masses and densities
-    Buf wts[6];      // asp_project2d_sph(_f64): fp32 working copies of m / rho * property
     int* h_counters = nullptr;  // pinned
     int morton_ntx = -1, morton_nty = -1;
     int morton3_key[3] = {-1, -1, -1};
@@ -171,30 +188,12 @@ struct Workspace {
     // End of the last call's GPU work on the workspace: the next call's stream waits for
     // it, so calls on different streams never overwrite buffers still being read.
     hipEvent_t last_ev = nullptr;
-    Buf morton3;  // brick order of the 3-D cube
     // Host -> device copies of pageable caller arrays go through two pinned bounce
     // buffers (h2d_staged): the CPU copy of one piece overlaps the DMA of the previous.
     void* pin[2] = {nullptr, nullptr};
     hipEvent_t pin_ev[2] = {};
     bool pin_busy[2] = {false, false};
     int pin_next = 0;
-    std::vector<Buf*> all_bufs() {
-        std::vector<Buf*> v = {&hist, &cmx, &tile_total, &tile_start, &tile_k, &items, &merges,
-                               &counters, &recs, &wide, &slabs, &morton, &morton3, &iorder,
-                               &ext};
-        for (auto& b : inx) v.push_back(&b);
-        for (auto& b : in) v.push_back(&b);
-        for (auto& b : out) v.push_back(&b);
-        for (auto& b : aux) v.push_back(&b);
-        for (auto& b : knn) v.push_back(&b);
-        for (auto& b : nearest) v.push_back(&b);
-        for (auto& b : match) v.push_back(&b);
-        for (auto& b : in64) v.push_back(&b);
-        for (auto& b : pairs) v.push_back(&b);
-        for (auto& b : inw) v.push_back(&b);
-        for (auto& b : wts) v.push_back(&b);
-        return v;
-    }
 };
 
 inline int ensure_side(Workspace& ws) {
@@ -213,11 +212,7 @@ inline int ensure_side(Workspace& ws) {
 // workspaces (g_ws) live for the process; asp_release frees only their buffers.
 void release_pinned(Workspace& ws);
 inline void ws_teardown(Workspace& ws) {
-    for (Buf* b : ws.all_bufs()) {
-        if (b->p) (void)hipFree(b->p);
-        b->p = nullptr;
-        b->cap = 0;
-    }
+    free_buffers(ws);
     if (ws.h_counters) (void)hipHostFree(ws.h_counters);
     ws.h_counters = nullptr;
     release_pinned(ws);
@@ -240,7 +235,8 @@ inline void ws_teardown(Workspace& ws) {
                 }
 }
 
-inline Workspace g_ws[64];
+constexpr int kMaxDevices = 64;  // devices the per-device tables below have room for
+inline Workspace g_ws[kMaxDevices];
 
 // 2-D maps from DIFFERENT streams get different workspaces (slots), so consecutive
 // independent maps enqueued on two streams overlap on the device (the binning of map
@@ -253,14 +249,14 @@ inline Workspace g_ws[64];
 #define ASP_MAP_SLOTS_MAX 2
 #endif
 constexpr int kMapSlots = ASP_MAP_SLOTS_MAX;
-inline Workspace g_ws_alt[64][kMapSlots - 1];
+inline Workspace g_ws_alt[kMaxDevices][kMapSlots - 1];
 struct SlotTable {
     std::mutex mu;
     hipStream_t stream[kMapSlots] = {};
     bool used[kMapSlots] = {};
     int last = kMapSlots - 1;
 };
-inline SlotTable g_slots[64];
+inline SlotTable g_slots[kMaxDevices];
 inline Workspace& slot_ws(int device, int s) { return s == 0 ? g_ws[device] : g_ws_alt[device][s - 1]; }
 inline int map_slot(int device, hipStream_t st) {
     static const int nslots = (int)env_int("ASP_MAP_SLOTS", kMapSlots, 1, kMapSlots);
@@ -288,7 +284,7 @@ struct DepositGate {
     hipEvent_t ev = nullptr;
     hipStream_t st = nullptr;
 };
-inline DepositGate g_gate[64];
+inline DepositGate g_gate[kMaxDevices];
 inline bool scatter_gate_on() { return env_int("ASP_SCATTER_GATE", 0) != 0; }
 inline int gate_wait(int device, hipStream_t st) {  // before a map's scatter
     DepositGate& G = g_gate[device];
@@ -308,7 +304,8 @@ inline int gate_record(int device, hipStream_t st) {  // after a map's deposit
 inline int set_device(int device) {
     int ndev = 0;
     ASP_HIP(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(ASP_ERR_INVALID, "bad device");
+    if (device < 0 || device >= std::min(ndev, kMaxDevices))
+        return fail(ASP_ERR_INVALID, "bad device");
     ASP_HIP(hipSetDevice(device));
     return ASP_OK;
 }
@@ -418,6 +415,54 @@ inline int ensure(Buf& b, size_t bytes) {
     }
     b.cap = want;
     if (env_set("ASP_PRINT_ALLOC")) fprintf(stderr, "asp alloc %zu B at %p\n", want, b.p);
+    return ASP_OK;
+}
+
+// The prologue and epilogue of every entry point that works in a shared workspace: the
+// device, the workspace under its lock -- the slot of the call's stream (map_slot: the 2-D
+// map and the cube) or the device's first -- ordered behind the workspace's previous call;
+// body(ws, st) is the call.  Every exit of the body records the end event (WsEnd).
+template <class F>
+inline int with_workspace(int device, hipStream_t st, bool per_stream_slot, F&& body) {
+    ASP_TRY(set_device(device));
+    Workspace& ws = per_stream_slot ? slot_ws(device, map_slot(device, st)) : g_ws[device];
+    std::lock_guard<std::mutex> lock(ws.mu);
+    ASP_TRY(ws_begin(ws, st));
+    WsEnd end(ws, st);
+    ASP_TRY(body(ws, st));
+    return end.finish();
+}
+
+// Host-array callers: arrays staged into workspace slots, results copied back.
+// How a host array reaches the device.  The two run at different speeds, so an entry
+// point keeps the one it was measured with.
+enum class Copy {
+    kPlain,   // hipMemcpyAsync from the caller's (pageable) array
+    kPinned   // h2d_staged: through the workspace's pinned bounce buffers
+};
+// Slot b holds `bytes` bytes at byte offset off; p points there.  (Arrays that share a slot:
+// the first one staged gives the whole size -- ensure() never shrinks, so the later ones
+// leave the slot in place.)
+template <class T>
+inline int device_scratch(Buf& b, T*& p, size_t bytes, size_t off = 0) {
+    ASP_TRY(ensure(b, off + bytes));
+    p = (T*)((char*)b.p + off);
+    return ASP_OK;
+}
+// ... and the host array p copied there on st; p is redirected to the copy.
+template <class T>
+inline int to_device(Workspace& ws, Buf& b, const T*& p, size_t bytes, hipStream_t st, Copy kind,
+                     size_t off = 0) {
+    const T* d = nullptr;
+    ASP_TRY(device_scratch(b, d, bytes, off));
+    if (bytes > 0 && kind == Copy::kPinned) ASP_TRY(h2d_staged(ws, (void*)d, p, bytes, st));
+    if (bytes > 0 && kind == Copy::kPlain)
+        ASP_HIP(hipMemcpyAsync((void*)d, p, bytes, hipMemcpyHostToDevice, st));
+    p = d;
+    return ASP_OK;
+}
+inline int to_host(void* dst, const void* src, size_t bytes, hipStream_t st) {
+    ASP_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
     return ASP_OK;
 }
 

@@ -22,8 +22,6 @@
 // one-lane-per-particle form, kept as a diagnostic; DESIGN.md §12 has the measurements.)
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -33,6 +31,7 @@
 
 #include "../../include/asp.h"
 #include "asp_host.hpp"
+#include "asp_prims.hpp"
 
 namespace asp {
 
@@ -1190,170 +1189,156 @@ static int knn(const double* pos, long long n, int k, double* h, int flags, int 
     if (n > 0 && (!pos || !h)) return fail(ASP_ERR_INVALID, "NULL array");
     if (n > 0x7fffffffLL) return fail(ASP_ERR_UNSUPPORTED, "n >= 2^31 particles per call");
     if (n == 0) return ASP_OK;
-    int ndev = 0;
-    ASP_HIP(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(ASP_ERR_INVALID, "bad device");
-    ASP_HIP(hipSetDevice(device));
-    Workspace& ws = g_ws[device];
-    std::lock_guard<std::mutex> lock(ws.mu);
-    ASP_TRY(ws_begin(ws, st));
-    WsEnd ws_end_(ws, st);
-    const bool dev = flags & ASP_F_DEVICE_PTRS;
-    const double* dpos = pos;
-    double* dh = h;
-    if (!dev) {
-        ASP_TRY(ensure(ws.knn[kKnnPos], (size_t)n * 3 * sizeof(double)));
-        ASP_TRY(ensure(ws.knn[kKnnH], (size_t)n * sizeof(double)));
-        ASP_HIP(hipMemcpyAsync(ws.knn[kKnnPos].p, pos, (size_t)n * 3 * sizeof(double),
-                               hipMemcpyHostToDevice, st));
-        dpos = (const double*)ws.knn[kKnnPos].p;
-        dh = (double*)ws.knn[kKnnH].p;
-    }
-    ASP_TRY(ensure(ws.knn[kKnnPartials], (size_t)kRedBlocks * 6 * sizeof(double) + 256));
-    ASP_TRY(ensure(ws.knn[kKnnKeys], (size_t)n * 2 * sizeof(unsigned long long)));  // keys in / out
-    ASP_TRY(ensure(ws.knn[kKnnIndex], (size_t)n * 2 * sizeof(int)));                 // index in / out
-    ASP_TRY(ensure(ws.knn[kKnnSorted], (size_t)n * 3 * sizeof(double)));              // sorted SoA
-    double* part = (double*)ws.knn[kKnnPartials].p;
-    KGrid* dg = (KGrid*)(part + kRedBlocks * 6);
-    unsigned long long* kin = (unsigned long long*)ws.knn[kKnnKeys].p;
-    unsigned long long* kout = kin + n;
-    int* iin = (int*)ws.knn[kKnnIndex].p;
-    int* iout = iin + n;
-    double* xs = (double*)ws.knn[kKnnSorted].p;
-    double *ys = xs + n, *zs = ys + n;
-    const unsigned nb = (unsigned)std::min<long long>(kRedBlocks, (n + kKnnBlock - 1) / kKnnBlock);
-    const unsigned grid = (unsigned)((n + kKnnBlock - 1) / kKnnBlock);
-    if (ws.prof) ASP_TRY(prof_next(ws));
-    StageMark mprep(ws, kSKnnPrep, st);  // bounding box, keys, sort, gather, cell tables
-    hipLaunchKernelGGL(k_bbox, dim3(nb), dim3(kKnnBlock), 0, st, dpos, (long long)n, part);
-    ASP_LAUNCHED();
-    hipLaunchKernelGGL(k_bbox_final, dim3(1), dim3(kKnnBlock), 0, st, (const double*)part, (int)nb, dg);
-    ASP_LAUNCHED();
-    hipLaunchKernelGGL(k_keys, dim3(grid), dim3(kKnnBlock), 0, st, dpos, (long long)n,
-                       (const KGrid*)dg, kin, iin);
-    ASP_LAUNCHED();
-    size_t tmp = 0;
-    ASP_HIP(rocprim::radix_sort_pairs(nullptr, tmp, kin, kout, iin, iout, (size_t)n, 0, 3 * kQBits,
-                                      st));
-    ASP_TRY(ensure(ws.knn[kKnnSortTmp], tmp));
-    ASP_HIP(rocprim::radix_sort_pairs(ws.knn[kKnnSortTmp].p, tmp, kin, kout, iin, iout, (size_t)n, 0,
-                                      3 * kQBits, st));
-    hipLaunchKernelGGL(k_gather, dim3(grid), dim3(kKnnBlock), 0, st, dpos, (long long)n,
-                       (const int*)iout, xs, ys, zs);
-    ASP_LAUNCHED();
-    // level-L cell table: about one particle per cell, at most 8^9 cells (512 MiB)
-    int L = 1;
-    while (L < 9 && (1LL << (3 * L)) < n) ++L;
-    const long long ncell = 1LL << (3 * L);
-    ASP_TRY(ensure(ws.knn[kKnnCells], (size_t)(ncell + 1) * sizeof(int)));
-    int* tab = (int*)ws.knn[kKnnCells].p;
-    ASP_HIP(hipMemsetD32Async((hipDeviceptr_t)tab, (int)n, (size_t)(ncell + 1), st));
-    hipLaunchKernelGGL(k_cell_starts, dim3(grid), dim3(kKnnBlock), 0, st,
-                       (const unsigned long long*)kout, (long long)n, kKeyBits - 3 * L, tab);
-    ASP_LAUNCHED();
-    {  // the empty cells: suffix minimum over the ncell + 1 entries
-        const long long m = ncell + 1;
-        const int nbs = (int)((m + kSfxSpan - 1) / kSfxSpan);
-        ASP_TRY(ensure(ws.knn[kKnnBlockMin], (size_t)nbs * sizeof(int)));
-        int* bmin = (int*)ws.knn[kKnnBlockMin].p;
-        hipLaunchKernelGGL(k_sfx_block, dim3(nbs), dim3(kSfxBlock), 0, st, tab, m, bmin);
+    return with_workspace(device, st, false, [&](Workspace& ws, hipStream_t st) -> int {
+        const bool dev = flags & ASP_F_DEVICE_PTRS;
+        const double* dpos = pos;
+        double* dh = h;
+        if (!dev) {
+            ASP_TRY(to_device(ws, ws.knn[kKnnPos], dpos, (size_t)n * 3 * sizeof(double), st,
+                              Copy::kPlain));
+            ASP_TRY(device_scratch(ws.knn[kKnnH], dh, (size_t)n * sizeof(double)));
+        }
+        ASP_TRY(ensure(ws.knn[kKnnPartials], (size_t)kRedBlocks * 6 * sizeof(double) + 256));
+        ASP_TRY(ensure(ws.knn[kKnnKeys], (size_t)n * 2 * sizeof(unsigned long long)));  // keys in / out
+        ASP_TRY(ensure(ws.knn[kKnnIndex], (size_t)n * 2 * sizeof(int)));                 // index in / out
+        ASP_TRY(ensure(ws.knn[kKnnSorted], (size_t)n * 3 * sizeof(double)));              // sorted SoA
+        double* part = (double*)ws.knn[kKnnPartials].p;
+        KGrid* dg = (KGrid*)(part + kRedBlocks * 6);
+        unsigned long long* kin = (unsigned long long*)ws.knn[kKnnKeys].p;
+        unsigned long long* kout = kin + n;
+        int* iin = (int*)ws.knn[kKnnIndex].p;
+        int* iout = iin + n;
+        double* xs = (double*)ws.knn[kKnnSorted].p;
+        double *ys = xs + n, *zs = ys + n;
+        const unsigned nb = (unsigned)std::min<long long>(kRedBlocks, (n + kKnnBlock - 1) / kKnnBlock);
+        const unsigned grid = (unsigned)((n + kKnnBlock - 1) / kKnnBlock);
+        if (ws.prof) ASP_TRY(prof_next(ws));
+        StageMark mprep(ws, kSKnnPrep, st);  // bounding box, keys, sort, gather, cell tables
+        hipLaunchKernelGGL(k_bbox, dim3(nb), dim3(kKnnBlock), 0, st, dpos, (long long)n, part);
         ASP_LAUNCHED();
-        hipLaunchKernelGGL(k_sfx_top, dim3(1), dim3(kSfxBlock), 0, st, bmin, nbs);
+        hipLaunchKernelGGL(k_bbox_final, dim3(1), dim3(kKnnBlock), 0, st, (const double*)part, (int)nb, dg);
         ASP_LAUNCHED();
-        hipLaunchKernelGGL(k_sfx_apply, dim3(nbs), dim3(kSfxBlock), 0, st, tab, m,
-                           (const int*)bmin, nbs);
+        hipLaunchKernelGGL(k_keys, dim3(grid), dim3(kKnnBlock), 0, st, dpos, (long long)n,
+                           (const KGrid*)dg, kin, iin);
         ASP_LAUNCHED();
-    }
-    // sub-tables of the dense level-L cells: at most n / (kSubMin + 1) of them
-    const int submin = (int)env_int("ASP_KNN_SUBMIN", kSubMin, 8);
-    const long long nslot_max = n / (submin + 1) + 1;
-    ASP_TRY(ensure(ws.knn[kKnnSubCells], (size_t)(ncell + 1) * sizeof(int)));
-    ASP_TRY(ensure(ws.knn[kKnnSubTable], (size_t)nslot_max * (kSubCells + 1) * sizeof(int)));
-    int* sub = (int*)ws.knn[kKnnSubCells].p;
-    int* nslot = sub + ncell;
-    int* subtab = (int*)ws.knn[kKnnSubTable].p;
-    ASP_HIP(hipMemsetAsync(nslot, 0, sizeof(int), st));
-    hipLaunchKernelGGL(k_sub_slots, dim3((unsigned)((ncell + kKnnBlock - 1) / kKnnBlock)),
-                       dim3(kKnnBlock), 0, st, (const int*)tab, ncell, submin, sub, nslot);
-    ASP_LAUNCHED();
-    hipLaunchKernelGGL(k_sub_table, dim3(grid), dim3(kKnnBlock), 0, st,
-                       (const unsigned long long*)kout, (long long)n, kKeyBits - 3 * L,
-                       (const int*)tab, (const int*)sub, subtab);
-    ASP_LAUNCHED();
-    const CellTab CT{tab, sub, subtab, kKeyBits - 3 * L};
-    mprep.done();
-    // diagnostics only: ASP_KNN_THREAD = one lane per particle throughout;
-    // ASP_KNN_DIAG = 1: the window pass alone (wrong results, timing)
-    const bool per_thread = env_set("ASP_KNN_THREAD");
-    const int diag = (int)env_int("ASP_KNN_DIAG", 0);
-    const int whalf = (int)env_int("ASP_KNN_WINDOW", kWinHalf);
-    const int fine = (int)env_int("ASP_KNN_FINE", kCellFine);
-    const int f32 = (int)env_int("ASP_KNN_F32", kWindowF32);
-    // the shared cell pass: the common level covers uq / 64 of a wave's lanes (0: off)
-    // the window / shared passes' entry test: 16 entries per step into a bit mask (1) or
-    // one entry per step into an 8-slot buffer (0)
-    const bool mask = env_int("ASP_KNN_MASK", kMaskTest) != 0;
-    // the window pass's chunk order: nearest to the wave's own first (1) or in array order (0)
-    const int near = (int)env_int("ASP_KNN_NEAR", kNearFirst);
-    // the window's first k entries sorted into the empty top-k (k == 32 / 64 only)
-    const int fill = (int)env_int("ASP_KNN_FILL", 1);
-    const int uq = (int)env_int("ASP_KNN_UNION", kUnionQ, 0, 64);
-    // ASP_KNN_COUNT: count the distances the search evaluates (bench.py's k-NN roofline;
-    // one atomic per lane, so off in timed runs) -> asp_last_stats [9] window, [10] cells,
-    // [11] entries the shared cell pass streamed (once per wave), [12] top-k insertions
-    unsigned long long* evc = nullptr;
-    if (env_set("ASP_KNN_COUNT")) {
-        ASP_TRY(ensure(ws.knn[kKnnCounters], 8 * sizeof(unsigned long long)));
-        evc = (unsigned long long*)ws.knn[kKnnCounters].p;
-        ASP_HIP(hipMemsetAsync(evc, 0, 8 * sizeof(unsigned long long), st));
-    }
-    StageMark msearch(ws, kSKnnSearch, st);
+        ASP_TRY(sort_pairs(ws.knn[kKnnSortTmp], kin, kout, iin, iout, (size_t)n, 3 * kQBits, st));
+        hipLaunchKernelGGL(k_gather, dim3(grid), dim3(kKnnBlock), 0, st, dpos, (long long)n,
+                           (const int*)iout, xs, ys, zs);
+        ASP_LAUNCHED();
+        // level-L cell table: about one particle per cell, at most 8^9 cells (512 MiB)
+        int L = 1;
+        while (L < 9 && (1LL << (3 * L)) < n) ++L;
+        const long long ncell = 1LL << (3 * L);
+        ASP_TRY(ensure(ws.knn[kKnnCells], (size_t)(ncell + 1) * sizeof(int)));
+        int* tab = (int*)ws.knn[kKnnCells].p;
+        ASP_HIP(hipMemsetD32Async((hipDeviceptr_t)tab, (int)n, (size_t)(ncell + 1), st));
+        hipLaunchKernelGGL(k_cell_starts, dim3(grid), dim3(kKnnBlock), 0, st,
+                           (const unsigned long long*)kout, (long long)n, kKeyBits - 3 * L, tab);
+        ASP_LAUNCHED();
+        {  // the empty cells: suffix minimum over the ncell + 1 entries
+            const long long m = ncell + 1;
+            const int nbs = (int)((m + kSfxSpan - 1) / kSfxSpan);
+            ASP_TRY(ensure(ws.knn[kKnnBlockMin], (size_t)nbs * sizeof(int)));
+            int* bmin = (int*)ws.knn[kKnnBlockMin].p;
+            hipLaunchKernelGGL(k_sfx_block, dim3(nbs), dim3(kSfxBlock), 0, st, tab, m, bmin);
+            ASP_LAUNCHED();
+            hipLaunchKernelGGL(k_sfx_top, dim3(1), dim3(kSfxBlock), 0, st, bmin, nbs);
+            ASP_LAUNCHED();
+            hipLaunchKernelGGL(k_sfx_apply, dim3(nbs), dim3(kSfxBlock), 0, st, tab, m,
+                               (const int*)bmin, nbs);
+            ASP_LAUNCHED();
+        }
+        // sub-tables of the dense level-L cells: at most n / (kSubMin + 1) of them
+        const int submin = (int)env_int("ASP_KNN_SUBMIN", kSubMin, 8);
+        const long long nslot_max = n / (submin + 1) + 1;
+        ASP_TRY(ensure(ws.knn[kKnnSubCells], (size_t)(ncell + 1) * sizeof(int)));
+        ASP_TRY(ensure(ws.knn[kKnnSubTable], (size_t)nslot_max * (kSubCells + 1) * sizeof(int)));
+        int* sub = (int*)ws.knn[kKnnSubCells].p;
+        int* nslot = sub + ncell;
+        int* subtab = (int*)ws.knn[kKnnSubTable].p;
+        ASP_HIP(hipMemsetAsync(nslot, 0, sizeof(int), st));
+        hipLaunchKernelGGL(k_sub_slots, dim3((unsigned)((ncell + kKnnBlock - 1) / kKnnBlock)),
+                           dim3(kKnnBlock), 0, st, (const int*)tab, ncell, submin, sub, nslot);
+        ASP_LAUNCHED();
+        hipLaunchKernelGGL(k_sub_table, dim3(grid), dim3(kKnnBlock), 0, st,
+                           (const unsigned long long*)kout, (long long)n, kKeyBits - 3 * L,
+                           (const int*)tab, (const int*)sub, subtab);
+        ASP_LAUNCHED();
+        const CellTab CT{tab, sub, subtab, kKeyBits - 3 * L};
+        mprep.done();
+        // diagnostics only: ASP_KNN_THREAD = one lane per particle throughout;
+        // ASP_KNN_DIAG = 1: the window pass alone (wrong results, timing)
+        const bool per_thread = env_set("ASP_KNN_THREAD");
+        const int diag = (int)env_int("ASP_KNN_DIAG", 0);
+        const int whalf = (int)env_int("ASP_KNN_WINDOW", kWinHalf);
+        const int fine = (int)env_int("ASP_KNN_FINE", kCellFine);
+        const int f32 = (int)env_int("ASP_KNN_F32", kWindowF32);
+        // the shared cell pass: the common level covers uq / 64 of a wave's lanes (0: off)
+        // the window / shared passes' entry test: 16 entries per step into a bit mask (1) or
+        // one entry per step into an 8-slot buffer (0)
+        const bool mask = env_int("ASP_KNN_MASK", kMaskTest) != 0;
+        // the window pass's chunk order: nearest to the wave's own first (1) or in array order (0)
+        const int near = (int)env_int("ASP_KNN_NEAR", kNearFirst);
+        // the window's first k entries sorted into the empty top-k (k == 32 / 64 only)
+        const int fill = (int)env_int("ASP_KNN_FILL", 1);
+        const int uq = (int)env_int("ASP_KNN_UNION", kUnionQ, 0, 64);
+        // ASP_KNN_COUNT: count the distances the search evaluates (bench.py's k-NN roofline;
+        // one atomic per lane, so off in timed runs) -> asp_last_stats [9] window, [10] cells,
+        // [11] entries the shared cell pass streamed (once per wave), [12] top-k insertions
+        unsigned long long* evc = nullptr;
+        if (env_set("ASP_KNN_COUNT")) {
+            ASP_TRY(ensure(ws.knn[kKnnCounters], 8 * sizeof(unsigned long long)));
+            evc = (unsigned long long*)ws.knn[kKnnCounters].p;
+            ASP_HIP(hipMemsetAsync(evc, 0, 8 * sizeof(unsigned long long), st));
+        }
+        StageMark msearch(ws, kSKnnSearch, st);
 #define ASP_KNN(KN)                                                                               \
-    do {                                                                                          \
-        if (per_thread)                                                                           \
-            hipLaunchKernelGGL(k_knn<KN>, dim3(grid), dim3(kKnnBlock), 0, st, (const double*)xs,  \
-                               (const double*)ys, (const double*)zs,                              \
-                               (const unsigned long long*)kout, (const int*)iout, (long long)n,   \
-                               k, (const KGrid*)dg, dh);                                          \
-        else if (mask)                                                                            \
-            hipLaunchKernelGGL((k_knn_wave<KN, true>), dim3((unsigned)((n + 255) / 256)),          \
-                               dim3(kKnnBlock), 0, st, (const double*)xs, (const double*)ys,      \
-                               (const double*)zs, (const unsigned long long*)kout,                \
-                               (const int*)iout, (long long)n, k, (const KGrid*)dg, dh, diag,     \
-                               whalf, fine, CT, f32, uq, near, fill, evc);                        \
-        else                                                                                      \
-            hipLaunchKernelGGL((k_knn_wave<KN, false>), dim3((unsigned)((n + 255) / 256)),         \
-                               dim3(kKnnBlock), 0, st, (const double*)xs, (const double*)ys,      \
-                               (const double*)zs, (const unsigned long long*)kout,                \
-                               (const int*)iout, (long long)n, k, (const KGrid*)dg, dh, diag,     \
-                               whalf, fine, CT, f32, uq, near, fill, evc);                        \
-    } while (0)
-    if (k <= 32)
-        ASP_KNN(32);
-    else
-        ASP_KNN(64);
+        do {                                                                                          \
+            if (per_thread)                                                                           \
+                hipLaunchKernelGGL(k_knn<KN>, dim3(grid), dim3(kKnnBlock), 0, st, (const double*)xs,  \
+                                   (const double*)ys, (const double*)zs,                              \
+                                   (const unsigned long long*)kout, (const int*)iout, (long long)n,   \
+                                   k, (const KGrid*)dg, dh);                                          \
+            else if (mask)                                                                            \
+                hipLaunchKernelGGL((k_knn_wave<KN, true>), dim3((unsigned)((n + 255) / 256)),          \
+                                   dim3(kKnnBlock), 0, st, (const double*)xs, (const double*)ys,      \
+                                   (const double*)zs, (const unsigned long long*)kout,                \
+                                   (const int*)iout, (long long)n, k, (const KGrid*)dg, dh, diag,     \
+                                   whalf, fine, CT, f32, uq, near, fill, evc);                        \
+            else                                                                                      \
+                hipLaunchKernelGGL((k_knn_wave<KN, false>), dim3((unsigned)((n + 255) / 256)),         \
+                                   dim3(kKnnBlock), 0, st, (const double*)xs, (const double*)ys,      \
+                                   (const double*)zs, (const unsigned long long*)kout,                \
+                                   (const int*)iout, (long long)n, k, (const KGrid*)dg, dh, diag,     \
+                                   whalf, fine, CT, f32, uq, near, fill, evc);                        \
+        } while (0)
+        if (k <= 32)
+            ASP_KNN(32);
+        else
+            ASP_KNN(64);
 #undef ASP_KNN
-    ASP_LAUNCHED();
-    msearch.done();
-    stats_clear(ws);  // (the map counters describe the last map no longer)
-    if (evc) {
-        unsigned long long e[8];
-        ASP_HIP(hipMemcpyAsync(e, evc, sizeof(e), hipMemcpyDeviceToHost, st));
-        ASP_HIP(hipStreamSynchronize(st));
-        ws.stats[9] = (long long)e[0];
-        ws.stats[10] = (long long)e[1];
-        ws.stats[11] = (long long)e[2];
-        ws.stats[12] = (long long)e[3];
-        if (env_set("ASP_KNN_COUNT_PRINT"))
-            fprintf(stderr, "knn shared pass: %llu waves, %.1f columns and %.1f ranges per wave\n", e[6],
-                    e[6] ? (double)e[4] / e[6] : 0.0, e[6] ? (double)e[5] / e[6] : 0.0);
-    }
-    if (!dev) {
-        ASP_HIP(hipMemcpyAsync(h, dh, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-        ASP_HIP(hipStreamSynchronize(st));
-    }
-    stats_publish(ws, device);
-    return ws_end_.finish();
+        ASP_LAUNCHED();
+        msearch.done();
+        stats_clear(ws);  // (the map counters describe the last map no longer)
+        if (evc) {
+            unsigned long long e[8];
+            ASP_HIP(hipMemcpyAsync(e, evc, sizeof(e), hipMemcpyDeviceToHost, st));
+            ASP_HIP(hipStreamSynchronize(st));
+            ws.stats[9] = (long long)e[0];
+            ws.stats[10] = (long long)e[1];
+            ws.stats[11] = (long long)e[2];
+            ws.stats[12] = (long long)e[3];
+            if (env_set("ASP_KNN_COUNT_PRINT"))
+                fprintf(stderr, "knn shared pass: %llu waves, %.1f columns and %.1f ranges per wave\n", e[6],
+                        e[6] ? (double)e[4] / e[6] : 0.0, e[6] ? (double)e[5] / e[6] : 0.0);
+        }
+        if (!dev) {
+            ASP_TRY(to_host(h, dh, (size_t)n * sizeof(double), st));
+            ASP_HIP(hipStreamSynchronize(st));
+        }
+        stats_publish(ws, device);
+        return ASP_OK;
+    });
 }
 
 }  // namespace asp

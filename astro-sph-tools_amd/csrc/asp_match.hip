@@ -23,14 +23,13 @@
 // atomicCAS(slot, EMPTY, r); equality is decided on keys[r], staged before the barrier.
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include <algorithm>
 #include <cstdint>
 #include <string>
 
 #include "../../include/asp.h"
 #include "asp_host.hpp"
+#include "asp_prims.hpp"
 
 namespace asp {
 
@@ -248,121 +247,103 @@ static int match_ids(const long long* S, const unsigned char* sf, long long ns, 
         std::fill(index, index + nt, -1);
         return ASP_OK;
     }
-    ASP_TRY(set_device(device));
-    Workspace& ws = g_ws[device];
-    std::lock_guard<std::mutex> lock(ws.mu);
-    ASP_TRY(ws_begin(ws, st));
-    WsEnd ws_end_(ws, st);
-    if (ns == 0) {
-        hipLaunchKernelGGL(k_mfill, dim3((unsigned)((nt + kMBlock - 1) / kMBlock)), dim3(kMBlock), 0, st,
-                           index, nt, -1);
-        ASP_LAUNCHED();
-        return ws_end_.finish();
-    }
-
-    // ---- tuning: keys per round, partitions ----
-    int K = (int)env_int("ASP_MATCH_CHUNK_KEYS", kMChunk, kMChunkMin, kMChunk);
-    while (K & (K - 1)) K &= K - 1;  // a power of two (rounded down), so 2K slots mask cleanly
-    int bits = 0;
-    while (bits < kMMaxBits && ((long long)(K / 2) << bits) < ns) ++bits;  // ~K/2 keys each
-    const long long P = 1LL << bits;
-    // ASP_MATCH_STOP (diagnostic, tools/match_bench.py): 1 = return after the count and the
-    // scans, 2 = after the scatter; the outputs are then meaningless.  Timing the three gives
-    // the phases' times without events inside the call.
-    const int stop = (int)env_int("ASP_MATCH_STOP", 3, 1, 3);
-
-    // ---- inputs on the device ----
-    const long long *dS = S, *dT = T;
-    const unsigned char *dsf = sf, *dtf = tf;
-    int* dindex = index;
-    unsigned char* dmatched = source_matched;
-    if (!dev) {
-        const size_t in_bytes = (size_t)(ns + nt) * 8;
-        ASP_TRY(ensure(ws.match[kMatchIds], in_bytes));
-        ASP_TRY(ensure(ws.match[kMatchFilters], (size_t)(ns + nt)));
-        ASP_TRY(ensure(ws.match[kMatchOutputs], (size_t)nt * 4 + (size_t)ns));
-        long long* d_ids = (long long*)ws.match[kMatchIds].p;
-        unsigned char* d_f = (unsigned char*)ws.match[kMatchFilters].p;
-        ASP_HIP(hipMemcpyAsync(d_ids, S, (size_t)ns * 8, hipMemcpyHostToDevice, st));
-        ASP_HIP(hipMemcpyAsync(d_ids + ns, T, (size_t)nt * 8, hipMemcpyHostToDevice, st));
-        dS = d_ids;
-        dT = d_ids + ns;
-        if (sf) {
-            ASP_HIP(hipMemcpyAsync(d_f, sf, (size_t)ns, hipMemcpyHostToDevice, st));
-            dsf = d_f;
+    return with_workspace(device, st, false, [&](Workspace& ws, hipStream_t st) -> int {
+        if (ns == 0) {
+            hipLaunchKernelGGL(k_mfill, dim3((unsigned)((nt + kMBlock - 1) / kMBlock)), dim3(kMBlock), 0, st,
+                               index, nt, -1);
+            ASP_LAUNCHED();
+            return ASP_OK;
         }
-        if (tf) {
-            ASP_HIP(hipMemcpyAsync(d_f + ns, tf, (size_t)nt, hipMemcpyHostToDevice, st));
-            dtf = d_f + ns;
+
+        // ---- tuning: keys per round, partitions ----
+        int K = (int)env_int("ASP_MATCH_CHUNK_KEYS", kMChunk, kMChunkMin, kMChunk);
+        while (K & (K - 1)) K &= K - 1;  // a power of two (rounded down), so 2K slots mask cleanly
+        int bits = 0;
+        while (bits < kMMaxBits && ((long long)(K / 2) << bits) < ns) ++bits;  // ~K/2 keys each
+        const long long P = 1LL << bits;
+        // ASP_MATCH_STOP (diagnostic, tools/match_bench.py): 1 = return after the count and the
+        // scans, 2 = after the scatter; the outputs are then meaningless.  Timing the three gives
+        // the phases' times without events inside the call.
+        const int stop = (int)env_int("ASP_MATCH_STOP", 3, 1, 3);
+
+        // ---- inputs on the device ----
+        const long long *dS = S, *dT = T;
+        const unsigned char *dsf = sf, *dtf = tf;
+        int* dindex = index;
+        unsigned char* dmatched = source_matched;
+        if (!dev) {
+            // one slot each for the IDs, the filters and the outputs, sized for both sides
+            // first: the source's part, then the target's
+            Buf &ids = ws.match[kMatchIds], &filters = ws.match[kMatchFilters];
+            ASP_TRY(ensure(ids, (size_t)(ns + nt) * 8));
+            ASP_TRY(to_device(ws, ids, dS, (size_t)ns * 8, st, Copy::kPlain));
+            ASP_TRY(to_device(ws, ids, dT, (size_t)nt * 8, st, Copy::kPlain, (size_t)ns * 8));
+            ASP_TRY(ensure(filters, (size_t)(ns + nt)));
+            if (sf) ASP_TRY(to_device(ws, filters, dsf, (size_t)ns, st, Copy::kPlain));
+            if (tf) ASP_TRY(to_device(ws, filters, dtf, (size_t)nt, st, Copy::kPlain, (size_t)ns));
+            ASP_TRY(ensure(ws.match[kMatchOutputs], (size_t)nt * 4 + (size_t)ns));
+            ASP_TRY(device_scratch(ws.match[kMatchOutputs], dindex, (size_t)nt * 4));
+            if (source_matched)
+                ASP_TRY(device_scratch(ws.match[kMatchOutputs], dmatched, (size_t)ns, (size_t)nt * 4));
         }
-        dindex = (int*)ws.match[kMatchOutputs].p;
-        dmatched = source_matched ? (unsigned char*)ws.match[kMatchOutputs].p + (size_t)nt * 4
-                                  : nullptr;
-    }
 
-    // ---- workspace: 2 x (P + 1) counts, 2 x (P + 1) starts, records (12 B per ID) ----
-    ASP_TRY(ensure(ws.match[kMatchPartCount], (size_t)(P + 1) * 2 * sizeof(int)));
-    ASP_TRY(ensure(ws.match[kMatchPartStart], (size_t)(P + 1) * 2 * sizeof(int)));
-    ASP_TRY(ensure(ws.match[kMatchKeys], (size_t)(ns + nt) * 8));
-    ASP_TRY(ensure(ws.match[kMatchPositions], (size_t)(ns + nt) * 4));
-    ASP_TRY(ensure(ws.match[kMatchCounters], 4 * sizeof(unsigned long long)));
-    int* scnt = (int*)ws.match[kMatchPartCount].p;
-    int* tcnt = scnt + (P + 1);
-    int* sstart = (int*)ws.match[kMatchPartStart].p;
-    int* tstart = sstart + (P + 1);
-    long long* skey = (long long*)ws.match[kMatchKeys].p;
-    long long* tkey = skey + ns;
-    int* sidx = (int*)ws.match[kMatchPositions].p;
-    int* tidx = sidx + ns;
-    unsigned long long* ctr = (unsigned long long*)ws.match[kMatchCounters].p;
-    // the counters after the join, plus [3]: records per side (filtered IDs) are the scans' ends
-    ASP_HIP(hipMemsetAsync(scnt, 0, (size_t)(P + 1) * 2 * sizeof(int), st));
-    ASP_HIP(hipMemsetAsync(ctr, 0, 4 * sizeof(unsigned long long), st));
-    if (dmatched) ASP_HIP(hipMemsetAsync(dmatched, 0, (size_t)ns, st));
+        // ---- workspace: 2 x (P + 1) counts, 2 x (P + 1) starts, records (12 B per ID) ----
+        ASP_TRY(ensure(ws.match[kMatchPartCount], (size_t)(P + 1) * 2 * sizeof(int)));
+        ASP_TRY(ensure(ws.match[kMatchPartStart], (size_t)(P + 1) * 2 * sizeof(int)));
+        ASP_TRY(ensure(ws.match[kMatchKeys], (size_t)(ns + nt) * 8));
+        ASP_TRY(ensure(ws.match[kMatchPositions], (size_t)(ns + nt) * 4));
+        ASP_TRY(ensure(ws.match[kMatchCounters], 4 * sizeof(unsigned long long)));
+        int* scnt = (int*)ws.match[kMatchPartCount].p;
+        int* tcnt = scnt + (P + 1);
+        int* sstart = (int*)ws.match[kMatchPartStart].p;
+        int* tstart = sstart + (P + 1);
+        long long* skey = (long long*)ws.match[kMatchKeys].p;
+        long long* tkey = skey + ns;
+        int* sidx = (int*)ws.match[kMatchPositions].p;
+        int* tidx = sidx + ns;
+        unsigned long long* ctr = (unsigned long long*)ws.match[kMatchCounters].p;
+        // the counters after the join, plus [3]: records per side (filtered IDs) are the scans' ends
+        ASP_HIP(hipMemsetAsync(scnt, 0, (size_t)(P + 1) * 2 * sizeof(int), st));
+        ASP_HIP(hipMemsetAsync(ctr, 0, 4 * sizeof(unsigned long long), st));
+        if (dmatched) ASP_HIP(hipMemsetAsync(dmatched, 0, (size_t)ns, st));
 
-    hipLaunchKernelGGL(k_mcount, dim3(match_grid(ns)), dim3(kMBlock), 0, st, dS, dsf, ns, bits, scnt,
-                       (int*)nullptr);
-    ASP_LAUNCHED();
-    hipLaunchKernelGGL(k_mcount, dim3(match_grid(nt)), dim3(kMBlock), 0, st, dT, dtf, nt, bits, tcnt,
-                       dindex);
-    ASP_LAUNCHED();
-    size_t tmp = 0;
-    ASP_HIP(rocprim::exclusive_scan(nullptr, tmp, scnt, sstart, 0, (size_t)(P + 1),
-                                    rocprim::plus<int>(), st));
-    ASP_TRY(ensure(ws.match[kMatchScanTmp], tmp));
-    ASP_HIP(rocprim::exclusive_scan(ws.match[kMatchScanTmp].p, tmp, scnt, sstart, 0, (size_t)(P + 1),
-                                    rocprim::plus<int>(), st));
-    ASP_HIP(rocprim::exclusive_scan(ws.match[kMatchScanTmp].p, tmp, tcnt, tstart, 0, (size_t)(P + 1),
-                                    rocprim::plus<int>(), st));
-    ASP_HIP(hipMemsetAsync(scnt, 0, (size_t)(P + 1) * 2 * sizeof(int), st));  // now the cursors
-    if (stop >= 2) {
-        hipLaunchKernelGGL(k_mscatter, dim3(match_grid(ns)), dim3(kMBlock), 0, st, dS, dsf, ns, bits,
-                           (const int*)sstart, scnt, skey, sidx, (int)ns);
+        hipLaunchKernelGGL(k_mcount, dim3(match_grid(ns)), dim3(kMBlock), 0, st, dS, dsf, ns, bits, scnt,
+                           (int*)nullptr);
         ASP_LAUNCHED();
-        hipLaunchKernelGGL(k_mscatter, dim3(match_grid(nt)), dim3(kMBlock), 0, st, dT, dtf, nt, bits,
-                           (const int*)tstart, tcnt, tkey, tidx, (int)nt);
+        hipLaunchKernelGGL(k_mcount, dim3(match_grid(nt)), dim3(kMBlock), 0, st, dT, dtf, nt, bits, tcnt,
+                           dindex);
         ASP_LAUNCHED();
-    }
+        ASP_TRY(exclusive_scan_int(ws.match[kMatchScanTmp], scnt, sstart, (size_t)(P + 1), st, tcnt,
+                                   tstart));
+        ASP_HIP(hipMemsetAsync(scnt, 0, (size_t)(P + 1) * 2 * sizeof(int), st));  // now the cursors
+        if (stop >= 2) {
+            hipLaunchKernelGGL(k_mscatter, dim3(match_grid(ns)), dim3(kMBlock), 0, st, dS, dsf, ns, bits,
+                               (const int*)sstart, scnt, skey, sidx, (int)ns);
+            ASP_LAUNCHED();
+            hipLaunchKernelGGL(k_mscatter, dim3(match_grid(nt)), dim3(kMBlock), 0, st, dT, dtf, nt, bits,
+                               (const int*)tstart, tcnt, tkey, tidx, (int)nt);
+            ASP_LAUNCHED();
+        }
 
-    const size_t lds = match_lds_bytes(K);
-    ASP_TRY(allow_dyn_lds((const void*)k_mjoin, lds));
-    if (stop >= 3) {
-        hipLaunchKernelGGL(k_mjoin, dim3((unsigned)P), dim3(kMBlock), lds, st, (const long long*)skey,
-                           (const int*)sidx, (const int*)sstart, (const long long*)tkey,
-                           (const int*)tidx, (const int*)tstart, K, dindex, dmatched, ctr);
-        ASP_LAUNCHED();
-    }
+        const size_t lds = match_lds_bytes(K);
+        ASP_TRY(allow_dyn_lds((const void*)k_mjoin, lds));
+        if (stop >= 3) {
+            hipLaunchKernelGGL(k_mjoin, dim3((unsigned)P), dim3(kMBlock), lds, st, (const long long*)skey,
+                               (const int*)sidx, (const int*)sstart, (const long long*)tkey,
+                               (const int*)tidx, (const int*)tstart, K, dindex, dmatched, ctr);
+            ASP_LAUNCHED();
+        }
 
-    unsigned long long h[3] = {0, 0, 0};
-    ASP_HIP(hipMemcpyAsync(h, ctr, sizeof(h), hipMemcpyDeviceToHost, st));
-    if (!dev) {
-        ASP_HIP(hipMemcpyAsync(index, dindex, (size_t)nt * 4, hipMemcpyDeviceToHost, st));
-        if (source_matched)
-            ASP_HIP(hipMemcpyAsync(source_matched, dmatched, (size_t)ns, hipMemcpyDeviceToHost, st));
-    }
-    ASP_HIP(hipStreamSynchronize(st));  // the counts decide the caller's exceptions
-    for (int k = 0; k < 3; ++k) counts[k] = (long long)h[k];
-    return ws_end_.finish();
+        unsigned long long h[3] = {0, 0, 0};
+        ASP_HIP(hipMemcpyAsync(h, ctr, sizeof(h), hipMemcpyDeviceToHost, st));
+        if (!dev) {
+            ASP_TRY(to_host(index, dindex, (size_t)nt * 4, st));
+            if (source_matched) ASP_TRY(to_host(source_matched, dmatched, (size_t)ns, st));
+        }
+        ASP_HIP(hipStreamSynchronize(st));  // the counts decide the caller's exceptions
+        for (int k = 0; k < 3; ++k) counts[k] = (long long)h[k];
+        return ASP_OK;
+    });
 }
 
 // ----------------------------------------------------------------------------------
@@ -438,61 +419,51 @@ static int take_rows(const void* data, long long n_rows, long long row_bytes, co
     if (n_rows > 0 && !data) return fail(ASP_ERR_INVALID, "data is NULL with n_rows > 0");
     if (n_rows > 0x80000000LL) return fail(ASP_ERR_UNSUPPORTED, "n_rows > 2^31: index is int32");
     if (n_index == 0) return ASP_OK;
-    ASP_TRY(set_device(device));
-    Workspace& ws = g_ws[device];
-    std::lock_guard<std::mutex> lock(ws.mu);
-    ASP_TRY(ws_begin(ws, st));
-    WsEnd ws_end_(ws, st);
-    const bool dev = flags & ASP_F_DEVICE_PTRS;
-    const void *ddata = data, *dfill = fill;
-    const int* dindex = index;
-    void* dout = out;
-    const size_t out_bytes = (size_t)n_index * (size_t)row_bytes;
-    if (!dev) {
-        const size_t rb16 = ((size_t)row_bytes + 15) / 16 * 16;
-        ASP_TRY(ensure(ws.match[kMatchRows], (size_t)n_rows * (size_t)row_bytes));
-        ASP_TRY(ensure(ws.match[kMatchRowsOut], out_bytes + rb16));
-        ASP_TRY(ensure(ws.match[kMatchRowIndex], (size_t)n_index * 4));
-        if (n_rows > 0)
-            ASP_HIP(hipMemcpyAsync(ws.match[kMatchRows].p, data, (size_t)n_rows * (size_t)row_bytes,
-                                   hipMemcpyHostToDevice, st));
-        ASP_HIP(hipMemcpyAsync(ws.match[kMatchRowIndex].p, index, (size_t)n_index * 4,
-                               hipMemcpyHostToDevice, st));
-        ddata = ws.match[kMatchRows].p;
-        dindex = (const int*)ws.match[kMatchRowIndex].p;
-        // the fill row first (16-byte slot), then the output
-        dout = (unsigned char*)ws.match[kMatchRowsOut].p + rb16;
-        if (fill) {
-            ASP_HIP(hipMemcpyAsync(ws.match[kMatchRowsOut].p, fill, (size_t)row_bytes,
-                                   hipMemcpyHostToDevice, st));
-            dfill = ws.match[kMatchRowsOut].p;
-        } else {  // unmatched rows keep the caller's bytes
-            ASP_HIP(hipMemcpyAsync(dout, out, out_bytes, hipMemcpyHostToDevice, st));
+    return with_workspace(device, st, false, [&](Workspace& ws, hipStream_t st) -> int {
+        const bool dev = flags & ASP_F_DEVICE_PTRS;
+        const void *ddata = data, *dfill = fill;
+        const int* dindex = index;
+        void* dout = out;
+        const size_t out_bytes = (size_t)n_index * (size_t)row_bytes;
+        if (!dev) {
+            const size_t rb16 = ((size_t)row_bytes + 15) / 16 * 16;
+            ASP_TRY(to_device(ws, ws.match[kMatchRows], ddata, (size_t)n_rows * (size_t)row_bytes, st,
+                              Copy::kPlain));
+            // one slot: the fill row first (16-byte slot), then the output
+            Buf& rows_out = ws.match[kMatchRowsOut];
+            ASP_TRY(device_scratch(rows_out, dout, out_bytes, rb16));
+            ASP_TRY(to_device(ws, ws.match[kMatchRowIndex], dindex, (size_t)n_index * 4, st,
+                              Copy::kPlain));
+            if (fill) {
+                ASP_TRY(to_device(ws, rows_out, dfill, (size_t)row_bytes, st, Copy::kPlain));
+            } else {  // unmatched rows keep the caller's bytes
+                ASP_HIP(hipMemcpyAsync(dout, out, out_bytes, hipMemcpyHostToDevice, st));
+            }
         }
-    }
-    ASP_TRY(ensure(ws.match[kMatchCounters], 4 * sizeof(unsigned long long)));
-    int* bad = (int*)ws.match[kMatchCounters].p;
-    ASP_HIP(hipMemsetAsync(bad, 0, sizeof(int), st));
-    // the widest unit that divides the row and that every pointer is aligned to
-    const uintptr_t al = (uintptr_t)ddata | (uintptr_t)dout | (uintptr_t)dfill | (uintptr_t)row_bytes;
-    if (al % 16 == 0)
-        launch_take<take16>(ddata, n_rows, row_bytes, dindex, n_index, dfill, dout, bad, st);
-    else if (al % 8 == 0)
-        launch_take<uint2>(ddata, n_rows, row_bytes, dindex, n_index, dfill, dout, bad, st);
-    else if (al % 4 == 0)
-        launch_take<unsigned>(ddata, n_rows, row_bytes, dindex, n_index, dfill, dout, bad, st);
-    else
-        launch_take<unsigned char>(ddata, n_rows, row_bytes, dindex, n_index, dfill, dout, bad, st);
-    ASP_LAUNCHED();
-    int h_bad = 0;
-    ASP_HIP(hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, st));
-    ASP_HIP(hipStreamSynchronize(st));
-    if (h_bad) return fail(ASP_ERR_INVALID, "an index is >= n_rows");
-    if (!dev) {
-        ASP_HIP(hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, st));
+        ASP_TRY(ensure(ws.match[kMatchCounters], 4 * sizeof(unsigned long long)));
+        int* bad = (int*)ws.match[kMatchCounters].p;
+        ASP_HIP(hipMemsetAsync(bad, 0, sizeof(int), st));
+        // the widest unit that divides the row and that every pointer is aligned to
+        const uintptr_t al = (uintptr_t)ddata | (uintptr_t)dout | (uintptr_t)dfill | (uintptr_t)row_bytes;
+        if (al % 16 == 0)
+            launch_take<take16>(ddata, n_rows, row_bytes, dindex, n_index, dfill, dout, bad, st);
+        else if (al % 8 == 0)
+            launch_take<uint2>(ddata, n_rows, row_bytes, dindex, n_index, dfill, dout, bad, st);
+        else if (al % 4 == 0)
+            launch_take<unsigned>(ddata, n_rows, row_bytes, dindex, n_index, dfill, dout, bad, st);
+        else
+            launch_take<unsigned char>(ddata, n_rows, row_bytes, dindex, n_index, dfill, dout, bad, st);
+        ASP_LAUNCHED();
+        int h_bad = 0;
+        ASP_HIP(hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, st));
         ASP_HIP(hipStreamSynchronize(st));
-    }
-    return ws_end_.finish();
+        if (h_bad) return fail(ASP_ERR_INVALID, "an index is >= n_rows");
+        if (!dev) {
+            ASP_TRY(to_host(out, dout, out_bytes, st));
+            ASP_HIP(hipStreamSynchronize(st));
+        }
+        return ASP_OK;
+    });
 }
 
 }  // namespace asp

@@ -27,8 +27,6 @@
 //     (1.07-6.6 times slower on a random-order input, DESIGN.md §17 has the A/B).
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
 #include <cmath>
@@ -39,6 +37,7 @@
 
 #include "../../include/asp.h"
 #include "asp_host.hpp"
+#include "asp_prims.hpp"
 
 namespace asp {
 
@@ -356,186 +355,167 @@ static int nearest(const double* pos, long long n, const double* centres, long l
     if (m > 0 && !centres) return fail(ASP_ERR_INVALID, "NULL centres");
     if (m > 0x7fffffffLL) return fail(ASP_ERR_UNSUPPORTED, "m >= 2^31 centres per call");
     if (n == 0) return ASP_OK;
-    int ndev = 0;
-    ASP_HIP(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(ASP_ERR_INVALID, "bad device");
-    ASP_HIP(hipSetDevice(device));
-    Workspace& ws = g_ws[device];
-    std::lock_guard<std::mutex> lock(ws.mu);
-    ASP_TRY(ws_begin(ws, st));
-    WsEnd ws_end_(ws, st);
-    const bool dev = flags & ASP_F_DEVICE_PTRS;
-    if (ws.prof) ASP_TRY(prof_next(ws));
-    stats_clear(ws);
+    return with_workspace(device, st, false, [&](Workspace& ws, hipStream_t st) -> int {
+        const bool dev = flags & ASP_F_DEVICE_PTRS;
+        if (ws.prof) ASP_TRY(prof_next(ws));
+        stats_clear(ws);
 
-    // ---- prep: the centres on the device, validated, counted, sorted by cell per set ----
-    StageMark mprep(ws, kSNearestPrep, st);
-    const double* dc = centres;
-    const unsigned* dm = member;
-    if (!dev && m > 0) {
-        ASP_TRY(ensure(ws.nearest[kNearCentres], (size_t)m * 3 * sizeof(double)));
-        ASP_HIP(hipMemcpyAsync(ws.nearest[kNearCentres].p, centres, (size_t)m * 3 * sizeof(double),
-                               hipMemcpyHostToDevice, st));
-        dc = (const double*)ws.nearest[kNearCentres].p;
-        if (member) {
-            ASP_TRY(ensure(ws.nearest[kNearMembers], (size_t)m * sizeof(unsigned)));
-            ASP_HIP(hipMemcpyAsync(ws.nearest[kNearMembers].p, member, (size_t)m * sizeof(unsigned),
-                                   hipMemcpyHostToDevice, st));
-            dm = (const unsigned*)ws.nearest[kNearMembers].p;
+        // ---- prep: the centres on the device, validated, counted, sorted by cell per set ----
+        StageMark mprep(ws, kSNearestPrep, st);
+        const double* dc = centres;
+        const unsigned* dm = member;
+        if (!dev && m > 0) {
+            ASP_TRY(to_device(ws, ws.nearest[kNearCentres], dc, (size_t)m * 3 * sizeof(double), st,
+                              Copy::kPlain));
+            if (member)
+                ASP_TRY(to_device(ws, ws.nearest[kNearMembers], dm, (size_t)m * sizeof(unsigned), st,
+                                  Copy::kPlain));
         }
-    }
-    const unsigned cgrid = (unsigned)((m + kNBlock - 1) / kNBlock);
-    int h[1 + kMaxSets] = {0};
-    if (m > 0) {
-        ASP_TRY(ensure(ws.nearest[kNearCheck], sizeof(h)));
-        int* dcnt = (int*)ws.nearest[kNearCheck].p;
-        ASP_HIP(hipMemsetAsync(dcnt, 0, sizeof(h), st));
-        hipLaunchKernelGGL(k_ncheck, dim3(cgrid), dim3(kNBlock), 0, st, dc, (long long)m, dm, nsets,
-                           L, dcnt);
-        ASP_LAUNCHED();
-        ASP_HIP(hipMemcpyAsync(h, dcnt, sizeof(h), hipMemcpyDeviceToHost, st));
-        ASP_HIP(hipStreamSynchronize(st));
-    }
-    if (h[0] & 4)
-        return fail(ASP_ERR_INVALID, "a centre coordinate is not finite (centres must lie inside "
-                                     "the periodic box [0, box_width))");
-    if (h[0] & 1)
-        return fail(ASP_ERR_INVALID, "a centre coordinate is >= box_width: outside the periodic box");
-    if (h[0] & 2)
-        return fail(ASP_ERR_INVALID, "a centre coordinate is negative: outside the periodic box");
-    const int small = (int)env_int("ASP_NEAREST_SMALL", kSmallSet, 0, 1 << 20);  // (tests raise it)
-    NTab T;
-    T.L = L;
-    T.halfL = 0.5 * L;
-    long long ncell = 0, nent = 0;
-    int gmax = 1;
-    for (int s = 0; s < kMaxSets; ++s) {
-        NSet& S = T.s[s];
-        S.M = s < nsets ? h[1 + s] : 0;
-        S.G = 0;
-        S.cell0 = (int)ncell;
-        S.first = (int)nent;
-        S.h = 0.0;
-        if (S.M == 0) continue;
-        S.G = S.M <= small ? 1
-                           : std::max(2, std::min(kMaxG, (int)std::floor(std::cbrt((double)S.M / kPerCell))));
-        S.h = L / (double)S.G;
-        ncell += (long long)S.G * S.G * S.G;
-        nent += S.M;
-        gmax = std::max(gmax, S.G);
-        if (nent > 0x7fffffffLL)
-            return fail(ASP_ERR_UNSUPPORTED, ">= 2^31 set members over all sets");
-    }
-    // (counts, then cursors)
-    ASP_TRY(ensure(ws.nearest[kNearCellCount], (size_t)(ncell + 1) * sizeof(int)));
-    ASP_TRY(ensure(ws.nearest[kNearCellStart], (size_t)(ncell + 1) * sizeof(int)));  // cell starts
-    ASP_TRY(ensure(ws.nearest[kNearEntries], (size_t)nent * sizeof(NEnt)));
-    int* cnt = (int*)ws.nearest[kNearCellCount].p;
-    int* start = (int*)ws.nearest[kNearCellStart].p;
-    NEnt* ent = (NEnt*)ws.nearest[kNearEntries].p;
-    if (nent > 0) {
-        ASP_HIP(hipMemsetAsync(cnt, 0, (size_t)(ncell + 1) * sizeof(int), st));
-        hipLaunchKernelGGL(k_ncount, dim3(cgrid), dim3(kNBlock), 0, st, dc, (long long)m, dm, nsets, T,
-                           cnt);
-        ASP_LAUNCHED();
-        size_t tmp = 0;
-        ASP_HIP(rocprim::exclusive_scan(nullptr, tmp, cnt, start, 0, (size_t)(ncell + 1),
-                                        rocprim::plus<int>(), st));
-        ASP_TRY(ensure(ws.nearest[kNearScanTmp], tmp));
-        ASP_HIP(rocprim::exclusive_scan(ws.nearest[kNearScanTmp].p, tmp, cnt, start, 0,
-                                        (size_t)(ncell + 1), rocprim::plus<int>(), st));
-        ASP_HIP(hipMemsetAsync(cnt, 0, (size_t)(ncell + 1) * sizeof(int), st));
-        hipLaunchKernelGGL(k_nfill, dim3(cgrid), dim3(kNBlock), 0, st, dc, (long long)m, dm, nsets, T,
-                           (const int*)start, cnt, ent);
-        ASP_LAUNCHED();
-    }
-    mprep.done();
-
-    // ---- search, in batches of queries ----
-    // ASP_NEAREST_COUNT: count the distances evaluated (one atomic per lane, so off in timed
-    // runs) -> asp_last_stats[9]
-    unsigned long long* evc = nullptr;
-    if (env_set("ASP_NEAREST_COUNT")) {
-        ASP_TRY(ensure(ws.nearest[kNearCounter], sizeof(unsigned long long)));
-        evc = (unsigned long long*)ws.nearest[kNearCounter].p;
-        ASP_HIP(hipMemsetAsync(evc, 0, sizeof(unsigned long long), st));
-    }
-    // ASP_NEAREST_SORT (read per call, so one process can time both): 1 = the queries of a
-    // batch are searched in the order of their cell key, 0 = in the caller's order
-    const bool sorted = env_int("ASP_NEAREST_SORT", kSortQueries) != 0;
-    // ASP_NEAREST_PRUNE=0: every cell of every shell is scanned (diagnostic; same results)
-    const int prune = env_int("ASP_NEAREST_PRUNE", 1) != 0;
-    const long long B = std::min(n, (long long)env_int("ASP_NEAREST_BATCH", kNBatch, 1, kNBatch));
-    if (!dev) {
-        ASP_TRY(ensure(ws.nearest[kNearQueries], (size_t)B * 3 * sizeof(double)));
-        ASP_TRY(ensure(ws.nearest[kNearOutputs],
-                       (size_t)B * nsets * (sizeof(double) + sizeof(int))));
-    }
-    unsigned *kin = nullptr, *kout = nullptr;
-    int *iin = nullptr, *iout = nullptr;
-    int key_bits = 3;
-    while ((1 << (key_bits / 3)) < gmax) key_bits += 3;
-    if (sorted) {
-        ASP_TRY(ensure(ws.nearest[kNearSortKeys], (size_t)B * 2 * sizeof(unsigned)));
-        ASP_TRY(ensure(ws.nearest[kNearSortIndex], (size_t)B * 2 * sizeof(int)));
-        kin = (unsigned*)ws.nearest[kNearSortKeys].p;
-        kout = kin + B;
-        iin = (int*)ws.nearest[kNearSortIndex].p;
-        iout = iin + B;
-    }
-    for (long long a = 0; a < n; a += B) {
-        const long long nb = std::min(B, n - a);
-        const unsigned grid = (unsigned)((nb + kNBlock - 1) / kNBlock);
-        const double* dpos = pos + 3 * a;
-        int* dindex = index + a;
-        double* ddist = distance + a;
-        long long ostride = n;
-        if (!dev) {
-            ASP_HIP(hipMemcpyAsync(ws.nearest[kNearQueries].p, pos + 3 * a,
-                                   (size_t)nb * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-            dpos = (const double*)ws.nearest[kNearQueries].p;
-            ddist = (double*)ws.nearest[kNearOutputs].p;
-            dindex = (int*)(ddist + (size_t)B * nsets);
-            ostride = B;
-        }
-        StageMark msearch(ws, kSNearestSearch, st);  // (with the query sort, when it is on)
-        if (sorted) {
-            hipLaunchKernelGGL(k_nkeys, dim3(grid), dim3(kNBlock), 0, st, dpos, nb, gmax, L, kin, iin);
+        const unsigned cgrid = (unsigned)((m + kNBlock - 1) / kNBlock);
+        int h[1 + kMaxSets] = {0};
+        if (m > 0) {
+            ASP_TRY(ensure(ws.nearest[kNearCheck], sizeof(h)));
+            int* dcnt = (int*)ws.nearest[kNearCheck].p;
+            ASP_HIP(hipMemsetAsync(dcnt, 0, sizeof(h), st));
+            hipLaunchKernelGGL(k_ncheck, dim3(cgrid), dim3(kNBlock), 0, st, dc, (long long)m, dm, nsets,
+                               L, dcnt);
             ASP_LAUNCHED();
-            size_t tmp = 0;
-            ASP_HIP(rocprim::radix_sort_pairs(nullptr, tmp, kin, kout, iin, iout, (size_t)nb, 0,
-                                              key_bits, st));
-            ASP_TRY(ensure(ws.nearest[kNearSortTmp], tmp));
-            ASP_HIP(rocprim::radix_sort_pairs(ws.nearest[kNearSortTmp].p, tmp, kin, kout, iin, iout,
-                                              (size_t)nb, 0, key_bits, st));
+            ASP_HIP(hipMemcpyAsync(h, dcnt, sizeof(h), hipMemcpyDeviceToHost, st));
+            ASP_HIP(hipStreamSynchronize(st));
         }
-        if (evc)
-            hipLaunchKernelGGL(k_nearest<true>, dim3(grid), dim3(kNBlock), 0, st, dpos, nb,
-                               (const int*)iout, T, nsets, (const NEnt*)ent, (const int*)start, dindex,
-                               ddist, ostride, prune, evc);
-        else
-            hipLaunchKernelGGL(k_nearest<false>, dim3(grid), dim3(kNBlock), 0, st, dpos, nb,
-                               (const int*)iout, T, nsets, (const NEnt*)ent, (const int*)start, dindex,
-                               ddist, ostride, prune, evc);
-        ASP_LAUNCHED();
-        msearch.done();
-        if (!dev)
-            for (int s = 0; s < nsets; ++s) {
-                ASP_HIP(hipMemcpyAsync(index + (size_t)s * n + a, dindex + (size_t)s * B,
-                                       (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, st));
-                ASP_HIP(hipMemcpyAsync(distance + (size_t)s * n + a, ddist + (size_t)s * B,
-                                       (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (h[0] & 4)
+            return fail(ASP_ERR_INVALID, "a centre coordinate is not finite (centres must lie inside "
+                                         "the periodic box [0, box_width))");
+        if (h[0] & 1)
+            return fail(ASP_ERR_INVALID, "a centre coordinate is >= box_width: outside the periodic box");
+        if (h[0] & 2)
+            return fail(ASP_ERR_INVALID, "a centre coordinate is negative: outside the periodic box");
+        const int small = (int)env_int("ASP_NEAREST_SMALL", kSmallSet, 0, 1 << 20);  // (tests raise it)
+        NTab T;
+        T.L = L;
+        T.halfL = 0.5 * L;
+        long long ncell = 0, nent = 0;
+        int gmax = 1;
+        for (int s = 0; s < kMaxSets; ++s) {
+            NSet& S = T.s[s];
+            S.M = s < nsets ? h[1 + s] : 0;
+            S.G = 0;
+            S.cell0 = (int)ncell;
+            S.first = (int)nent;
+            S.h = 0.0;
+            if (S.M == 0) continue;
+            S.G = S.M <= small ? 1
+                               : std::max(2, std::min(kMaxG, (int)std::floor(std::cbrt((double)S.M / kPerCell))));
+            S.h = L / (double)S.G;
+            ncell += (long long)S.G * S.G * S.G;
+            nent += S.M;
+            gmax = std::max(gmax, S.G);
+            if (nent > 0x7fffffffLL)
+                return fail(ASP_ERR_UNSUPPORTED, ">= 2^31 set members over all sets");
+        }
+        // (counts, then cursors)
+        ASP_TRY(ensure(ws.nearest[kNearCellCount], (size_t)(ncell + 1) * sizeof(int)));
+        ASP_TRY(ensure(ws.nearest[kNearCellStart], (size_t)(ncell + 1) * sizeof(int)));  // cell starts
+        ASP_TRY(ensure(ws.nearest[kNearEntries], (size_t)nent * sizeof(NEnt)));
+        int* cnt = (int*)ws.nearest[kNearCellCount].p;
+        int* start = (int*)ws.nearest[kNearCellStart].p;
+        NEnt* ent = (NEnt*)ws.nearest[kNearEntries].p;
+        if (nent > 0) {
+            ASP_HIP(hipMemsetAsync(cnt, 0, (size_t)(ncell + 1) * sizeof(int), st));
+            hipLaunchKernelGGL(k_ncount, dim3(cgrid), dim3(kNBlock), 0, st, dc, (long long)m, dm, nsets, T,
+                               cnt);
+            ASP_LAUNCHED();
+            ASP_TRY(exclusive_scan_int(ws.nearest[kNearScanTmp], cnt, start, (size_t)(ncell + 1), st));
+            ASP_HIP(hipMemsetAsync(cnt, 0, (size_t)(ncell + 1) * sizeof(int), st));
+            hipLaunchKernelGGL(k_nfill, dim3(cgrid), dim3(kNBlock), 0, st, dc, (long long)m, dm, nsets, T,
+                               (const int*)start, cnt, ent);
+            ASP_LAUNCHED();
+        }
+        mprep.done();
+
+        // ---- search, in batches of queries ----
+        // ASP_NEAREST_COUNT: count the distances evaluated (one atomic per lane, so off in timed
+        // runs) -> asp_last_stats[9]
+        unsigned long long* evc = nullptr;
+        if (env_set("ASP_NEAREST_COUNT")) {
+            ASP_TRY(ensure(ws.nearest[kNearCounter], sizeof(unsigned long long)));
+            evc = (unsigned long long*)ws.nearest[kNearCounter].p;
+            ASP_HIP(hipMemsetAsync(evc, 0, sizeof(unsigned long long), st));
+        }
+        // ASP_NEAREST_SORT (read per call, so one process can time both): 1 = the queries of a
+        // batch are searched in the order of their cell key, 0 = in the caller's order
+        const bool sorted = env_int("ASP_NEAREST_SORT", kSortQueries) != 0;
+        // ASP_NEAREST_PRUNE=0: every cell of every shell is scanned (diagnostic; same results)
+        const int prune = env_int("ASP_NEAREST_PRUNE", 1) != 0;
+        const long long B = std::min(n, (long long)env_int("ASP_NEAREST_BATCH", kNBatch, 1, kNBatch));
+        // a batch's outputs share a slot: B * nsets distances, then as many indices
+        const size_t dist_bytes = (size_t)B * nsets * sizeof(double);
+        if (!dev) {  // (both up front, in this order: where the slots land is part of the speed)
+            ASP_TRY(ensure(ws.nearest[kNearQueries], (size_t)B * 3 * sizeof(double)));
+            ASP_TRY(ensure(ws.nearest[kNearOutputs], dist_bytes + (size_t)B * nsets * sizeof(int)));
+        }
+        unsigned *kin = nullptr, *kout = nullptr;
+        int *iin = nullptr, *iout = nullptr;
+        int key_bits = 3;
+        while ((1 << (key_bits / 3)) < gmax) key_bits += 3;
+        if (sorted) {
+            ASP_TRY(ensure(ws.nearest[kNearSortKeys], (size_t)B * 2 * sizeof(unsigned)));
+            ASP_TRY(ensure(ws.nearest[kNearSortIndex], (size_t)B * 2 * sizeof(int)));
+            kin = (unsigned*)ws.nearest[kNearSortKeys].p;
+            kout = kin + B;
+            iin = (int*)ws.nearest[kNearSortIndex].p;
+            iout = iin + B;
+        }
+        for (long long a = 0; a < n; a += B) {
+            const long long nb = std::min(B, n - a);
+            const unsigned grid = (unsigned)((nb + kNBlock - 1) / kNBlock);
+            const double* dpos = pos + 3 * a;
+            int* dindex = index + a;
+            double* ddist = distance + a;
+            long long ostride = n;
+            if (!dev) {
+                ASP_TRY(to_device(ws, ws.nearest[kNearQueries], dpos, (size_t)nb * 3 * sizeof(double),
+                                  st, Copy::kPlain));
+                ASP_TRY(device_scratch(ws.nearest[kNearOutputs], ddist, dist_bytes));
+                ASP_TRY(device_scratch(ws.nearest[kNearOutputs], dindex, (size_t)B * nsets * sizeof(int),
+                                       dist_bytes));
+                ostride = B;
             }
-    }
-    if (evc) {
-        unsigned long long e = 0;
-        ASP_HIP(hipMemcpyAsync(&e, evc, sizeof(e), hipMemcpyDeviceToHost, st));
-        ASP_HIP(hipStreamSynchronize(st));
-        ws.stats[9] = (long long)e;
-    }
-    if (!dev) ASP_HIP(hipStreamSynchronize(st));
-    stats_publish(ws, device);
-    return ws_end_.finish();
+            StageMark msearch(ws, kSNearestSearch, st);  // (with the query sort, when it is on)
+            if (sorted) {
+                hipLaunchKernelGGL(k_nkeys, dim3(grid), dim3(kNBlock), 0, st, dpos, nb, gmax, L, kin, iin);
+                ASP_LAUNCHED();
+                ASP_TRY(sort_pairs(ws.nearest[kNearSortTmp], kin, kout, iin, iout, (size_t)nb, key_bits,
+                                   st));
+            }
+            if (evc)
+                hipLaunchKernelGGL(k_nearest<true>, dim3(grid), dim3(kNBlock), 0, st, dpos, nb,
+                                   (const int*)iout, T, nsets, (const NEnt*)ent, (const int*)start, dindex,
+                                   ddist, ostride, prune, evc);
+            else
+                hipLaunchKernelGGL(k_nearest<false>, dim3(grid), dim3(kNBlock), 0, st, dpos, nb,
+                                   (const int*)iout, T, nsets, (const NEnt*)ent, (const int*)start, dindex,
+                                   ddist, ostride, prune, evc);
+            ASP_LAUNCHED();
+            msearch.done();
+            if (!dev)
+                for (int s = 0; s < nsets; ++s) {
+                    ASP_TRY(to_host(index + (size_t)s * n + a, dindex + (size_t)s * B,
+                                    (size_t)nb * sizeof(int), st));
+                    ASP_TRY(to_host(distance + (size_t)s * n + a, ddist + (size_t)s * B,
+                                    (size_t)nb * sizeof(double), st));
+                }
+        }
+        if (evc) {
+            unsigned long long e = 0;
+            ASP_HIP(hipMemcpyAsync(&e, evc, sizeof(e), hipMemcpyDeviceToHost, st));
+            ASP_HIP(hipStreamSynchronize(st));
+            ws.stats[9] = (long long)e;
+        }
+        if (!dev) ASP_HIP(hipStreamSynchronize(st));
+        stats_publish(ws, device);
+        return ASP_OK;
+    });
 }
 
 }  // namespace asp

@@ -234,13 +234,10 @@ static int pairs_begin(const double* pos, const double* h, long long n, int axis
     const bool dev = flags & ASP_F_DEVICE_PTRS;
     const double *dpos = pos, *dh64 = h;
     if (!dev && n > 0) {
-        int rc = ensure(ws.in64[0], (size_t)n * 3 * sizeof(double));
-        if (rc == ASP_OK) rc = ensure(ws.in64[1], (size_t)n * sizeof(double));
-        if (rc == ASP_OK) rc = h2d_staged(ws, ws.in64[0].p, pos, (size_t)n * 3 * sizeof(double), S->st);
-        if (rc == ASP_OK) rc = h2d_staged(ws, ws.in64[1].p, h, (size_t)n * sizeof(double), S->st);
+        int rc = to_device(ws, ws.in64[0], dpos, (size_t)n * 3 * sizeof(double), S->st, Copy::kPinned);
+        if (rc == ASP_OK)
+            rc = to_device(ws, ws.in64[1], dh64, (size_t)n * sizeof(double), S->st, Copy::kPinned);
         if (rc != ASP_OK) return bail(rc);
-        dpos = (const double*)ws.in64[0].p;
-        dh64 = (const double*)ws.in64[1].p;
     }
     for (int k = 0; k < 3; ++k) {
         const int rc = ensure(ws.in[k], (size_t)n * sizeof(float));
@@ -295,12 +292,9 @@ static int pairs_emit(PairsSession& S, int t0, int t1, long long* offsets, int* 
     int* dpart = particle;
     double* dr2 = r2;
     if (!dev) {
-        ASP_TRY(ensure(ws.aux[kOffsets], (size_t)(npx + 1) * sizeof(long long)));
-        ASP_TRY(ensure(ws.aux[kParticle], (size_t)std::max(total, 1LL) * sizeof(int)));
-        ASP_TRY(ensure(ws.aux[kR2], (size_t)std::max(total, 1LL) * sizeof(double)));
-        doff = (long long*)ws.aux[kOffsets].p;
-        dpart = (int*)ws.aux[kParticle].p;
-        dr2 = (double*)ws.aux[kR2].p;
+        ASP_TRY(device_scratch(ws.aux[kOffsets], doff, (size_t)(npx + 1) * sizeof(long long)));
+        ASP_TRY(device_scratch(ws.aux[kParticle], dpart, (size_t)std::max(total, 1LL) * sizeof(int)));
+        ASP_TRY(device_scratch(ws.aux[kR2], dr2, (size_t)std::max(total, 1LL) * sizeof(double)));
     }
     ASP_TRY(ensure(ws.aux[kTileBase], (size_t)(t1 - t0 + 1) * sizeof(long long)));
     ASP_TRY(ensure(ws.aux[kOverflow], sizeof(int)));
@@ -344,13 +338,10 @@ static int pairs_emit(PairsSession& S, int t0, int t1, long long* offsets, int* 
     int ovf = 0;
     ASP_HIP(hipMemcpyAsync(&ovf, dovf, sizeof(int), hipMemcpyDeviceToHost, S.st));
     if (!dev) {
-        ASP_HIP(hipMemcpyAsync(offsets, doff, (size_t)(npx + 1) * sizeof(long long),
-                               hipMemcpyDeviceToHost, S.st));
+        ASP_TRY(to_host(offsets, doff, (size_t)(npx + 1) * sizeof(long long), S.st));
         if (total > 0) {
-            ASP_HIP(hipMemcpyAsync(particle, dpart, (size_t)total * sizeof(int),
-                                   hipMemcpyDeviceToHost, S.st));
-            ASP_HIP(hipMemcpyAsync(r2, dr2, (size_t)total * sizeof(double), hipMemcpyDeviceToHost,
-                                   S.st));
+            ASP_TRY(to_host(particle, dpart, (size_t)total * sizeof(int), S.st));
+            ASP_TRY(to_host(r2, dr2, (size_t)total * sizeof(double), S.st));
         }
     }
     ASP_HIP(hipStreamSynchronize(S.st));

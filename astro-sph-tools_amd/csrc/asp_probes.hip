@@ -117,33 +117,24 @@ int asp_kernel_eval(int32_t kernel_id, const double* r, const double* h, double*
     if (kernel_id < 0 || kernel_id > 2) return fail(ASP_ERR_INVALID, "unknown kernel_id");
     if (n < 0) return fail(ASP_ERR_INVALID, "n < 0");
     if (n == 0) return ASP_OK;
-    ASP_TRY(set_device(device));
-    Workspace& ws = g_ws[device];
-    std::lock_guard<std::mutex> lock(ws.mu);
-    hipStream_t st = (hipStream_t)stream;
-    ASP_TRY(ws_begin(ws, st));
-    WsEnd ws_end_(ws, st);
-    const double *dr = r, *dh = h;
-    double* dw = w;
-    bool dev = flags & ASP_F_DEVICE_PTRS;
-    if (!dev) {
-        ASP_TRY(ensure(ws.aux[kR], n * sizeof(double)));
-        ASP_TRY(ensure(ws.aux[kH], n * sizeof(double)));
-        ASP_TRY(ensure(ws.aux[kW], n * sizeof(double)));
-        ASP_HIP(hipMemcpyAsync(ws.aux[kR].p, r, n * sizeof(double), hipMemcpyHostToDevice, st));
-        ASP_HIP(hipMemcpyAsync(ws.aux[kH].p, h, n * sizeof(double), hipMemcpyHostToDevice, st));
-        dr = (const double*)ws.aux[kR].p;
-        dh = (const double*)ws.aux[kH].p;
-        dw = (double*)ws.aux[kW].p;
-    }
-    hipLaunchKernelGGL(k_kernel_eval, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                       (int)kernel_id, dr, dh, dw, (long long)n);
-    ASP_HIP(hipGetLastError());
-    if (!dev) {
-        ASP_HIP(hipMemcpyAsync(w, dw, n * sizeof(double), hipMemcpyDeviceToHost, st));
-        ASP_HIP(hipStreamSynchronize(st));
-    }
-    return ws_end_.finish();
+    return with_workspace(device, (hipStream_t)stream, false, [&](Workspace& ws, hipStream_t st) -> int {
+        const double *dr = r, *dh = h;
+        double* dw = w;
+        bool dev = flags & ASP_F_DEVICE_PTRS;
+        if (!dev) {
+            ASP_TRY(to_device(ws, ws.aux[kR], dr, n * sizeof(double), st, Copy::kPlain));
+            ASP_TRY(to_device(ws, ws.aux[kH], dh, n * sizeof(double), st, Copy::kPlain));
+            ASP_TRY(device_scratch(ws.aux[kW], dw, n * sizeof(double)));
+        }
+        hipLaunchKernelGGL(k_kernel_eval, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
+                           (int)kernel_id, dr, dh, dw, (long long)n);
+        ASP_LAUNCHED();
+        if (!dev) {
+            ASP_TRY(to_host(w, dw, n * sizeof(double), st));
+            ASP_HIP(hipStreamSynchronize(st));
+        }
+        return ASP_OK;
+    });
 }
 
 int asp_chunk_ranges(const float* u, const float* v, const float* h, int64_t n, double u_min,
@@ -156,40 +147,27 @@ int asp_chunk_ranges(const float* u, const float* v, const float* h, int64_t n, 
         return fail(ASP_ERR_INVALID, "invalid grid");
     if (n < 0) return fail(ASP_ERR_INVALID, "n < 0");
     if (n == 0) return ASP_OK;
-    ASP_TRY(set_device(device));
-    Workspace& ws = g_ws[device];
-    std::lock_guard<std::mutex> lock(ws.mu);
-    hipStream_t st = (hipStream_t)stream;
-    ASP_TRY(ws_begin(ws, st));
-    WsEnd ws_end_(ws, st);
-    bool dev = flags & ASP_F_DEVICE_PTRS;
-    const float *du = u, *dv = v, *dh = h;
-    int* o[4] = {cx0, cx1, cy0, cy1};
-    if (!dev) {
-        const float* src[3] = {u, v, h};
-        for (int k = 0; k < 3; ++k) {
-            ASP_TRY(ensure(ws.in[k], n * sizeof(float)));
-            ASP_HIP(hipMemcpyAsync(ws.in[k].p, src[k], n * sizeof(float), hipMemcpyHostToDevice,
-                                   st));
+    return with_workspace(device, (hipStream_t)stream, false, [&](Workspace& ws, hipStream_t st) -> int {
+        bool dev = flags & ASP_F_DEVICE_PTRS;
+        const float *du = u, *dv = v, *dh = h;
+        int* o[4] = {cx0, cx1, cy0, cy1};
+        if (!dev) {
+            const float** src[3] = {&du, &dv, &dh};
+            for (int k = 0; k < 3; ++k)
+                ASP_TRY(to_device(ws, ws.in[k], *src[k], n * sizeof(float), st, Copy::kPlain));
+            for (int k = 0; k < 4; ++k) ASP_TRY(device_scratch(ws.aux[k], o[k], n * sizeof(int)));
         }
-        du = (const float*)ws.in[0].p;
-        dv = (const float*)ws.in[1].p;
-        dh = (const float*)ws.in[2].p;
-        for (int k = 0; k < 4; ++k) {
-            ASP_TRY(ensure(ws.aux[k], n * sizeof(int)));
-            o[k] = (int*)ws.aux[k].p;
+        hipLaunchKernelGGL(k_chunk_ranges, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g,
+                           du, dv, dh, (long long)n, o[0], o[1], o[2], o[3]);
+        ASP_LAUNCHED();
+        if (!dev) {
+            int* dst[4] = {cx0, cx1, cy0, cy1};
+            for (int k = 0; k < 4; ++k)
+                ASP_TRY(to_host(dst[k], o[k], n * sizeof(int), st));
+            ASP_HIP(hipStreamSynchronize(st));
         }
-    }
-    hipLaunchKernelGGL(k_chunk_ranges, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g,
-                       du, dv, dh, (long long)n, o[0], o[1], o[2], o[3]);
-    ASP_HIP(hipGetLastError());
-    if (!dev) {
-        int* dst[4] = {cx0, cx1, cy0, cy1};
-        for (int k = 0; k < 4; ++k)
-            ASP_HIP(hipMemcpyAsync(dst[k], o[k], n * sizeof(int), hipMemcpyDeviceToHost, st));
-        ASP_HIP(hipStreamSynchronize(st));
-    }
-    return ws_end_.finish();
+        return ASP_OK;
+    });
 }
 
 int asp_pixel_neighbours(const float* u, const float* v, const float* h, int64_t n,
@@ -214,54 +192,40 @@ int asp_pixel_neighbours(const float* u, const float* v, const float* h, int64_t
         for (int64_t k = 0; k < npix; ++k) offsets[k + 1] = 0;
         return ASP_OK;
     }
-    ASP_TRY(set_device(device));
-    Workspace& ws = g_ws[device];
-    std::lock_guard<std::mutex> lock(ws.mu);
-    hipStream_t st = nullptr;
-    ASP_TRY(ws_begin(ws, st));
-    WsEnd ws_end_(ws, st);
-    const float* src[3] = {u, v, h};
-    for (int k = 0; k < 3; ++k) {
-        ASP_TRY(ensure(ws.in[k], n * sizeof(float)));
-        ASP_HIP(hipMemcpyAsync(ws.in[k].p, src[k], n * sizeof(float), hipMemcpyHostToDevice, st));
-    }
-    ASP_TRY(ensure(ws.aux[kPixels], npix * sizeof(long long)));
-    ASP_TRY(ensure(ws.aux[kCounts], npix * sizeof(long long)));
-    ASP_TRY(ensure(ws.aux[kOffsets], (npix + 1) * sizeof(long long)));
-    ASP_HIP(hipMemcpyAsync(ws.aux[kPixels].p, pixels, npix * sizeof(long long),
-                           hipMemcpyHostToDevice, st));
-    const Src64 s{nullptr, nullptr, nullptr, nullptr, nullptr, 0, (const float*)ws.in[0].p,
-                  (const float*)ws.in[1].p, (const float*)ws.in[2].p};
-    hipLaunchKernelGGL(k_neighbours, dim3((unsigned)npix), dim3(kBlock), 0, st, g, s,
-                       (const float*)ws.in[0].p, (const float*)ws.in[1].p,
-                       (const float*)ws.in[2].p, (long long)n,
-                       (const long long*)ws.aux[kPixels].p, (long long*)ws.aux[kCounts].p,
-                       (const long long*)nullptr, (int*)nullptr, 0LL, 0);
-    ASP_HIP(hipGetLastError());
-    std::vector<long long> cnt(npix);
-    ASP_HIP(hipMemcpyAsync(cnt.data(), ws.aux[kCounts].p, npix * sizeof(long long),
-                           hipMemcpyDeviceToHost, st));
-    ASP_HIP(hipStreamSynchronize(st));
-    for (int64_t k = 0; k < npix; ++k) offsets[k + 1] = offsets[k] + cnt[k];
-    long long tot = offsets[npix];
-    if (total) *total = tot;
-    long long wcap = std::min<long long>(cap, tot);
-    if (wcap > 0) {
-        ASP_TRY(ensure(ws.aux[kIndex], wcap * sizeof(int)));
-        ASP_HIP(hipMemcpyAsync(ws.aux[kOffsets].p, offsets, npix * sizeof(long long),
-                               hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_neighbours, dim3((unsigned)npix), dim3(kBlock), 0, st, g, s,
-                           (const float*)ws.in[0].p, (const float*)ws.in[1].p,
-                           (const float*)ws.in[2].p, (long long)n,
-                           (const long long*)ws.aux[kPixels].p, (long long*)ws.aux[kCounts].p,
-                           (const long long*)ws.aux[kOffsets].p,
-                           (int*)ws.aux[kIndex].p, wcap, 1);
-        ASP_HIP(hipGetLastError());
-        ASP_HIP(hipMemcpyAsync(index, ws.aux[kIndex].p, wcap * sizeof(int), hipMemcpyDeviceToHost,
-                               st));
+    return with_workspace(device, nullptr, false, [&](Workspace& ws, hipStream_t st) -> int {
+        const float* d[3] = {u, v, h};
+        for (int k = 0; k < 3; ++k)
+            ASP_TRY(to_device(ws, ws.in[k], d[k], n * sizeof(float), st, Copy::kPlain));
+        const long long* dpix = (const long long*)pixels;
+        long long* dcnt = nullptr;
+        ASP_TRY(to_device(ws, ws.aux[kPixels], dpix, npix * sizeof(long long), st, Copy::kPlain));
+        ASP_TRY(device_scratch(ws.aux[kCounts], dcnt, npix * sizeof(long long)));
+        ASP_TRY(ensure(ws.aux[kOffsets], (npix + 1) * sizeof(long long)));
+        const Src64 s{nullptr, nullptr, nullptr, nullptr, nullptr, 0, d[0], d[1], d[2]};
+        hipLaunchKernelGGL(k_neighbours, dim3((unsigned)npix), dim3(kBlock), 0, st, g, s, d[0], d[1],
+                           d[2], (long long)n, dpix, dcnt, (const long long*)nullptr, (int*)nullptr,
+                           0LL, 0);
+        ASP_LAUNCHED();
+        std::vector<long long> cnt(npix);
+        ASP_TRY(to_host(cnt.data(), dcnt, npix * sizeof(long long), st));
         ASP_HIP(hipStreamSynchronize(st));
-    }
-    return ws_end_.finish();
+        for (int64_t k = 0; k < npix; ++k) offsets[k + 1] = offsets[k] + cnt[k];
+        long long tot = offsets[npix];
+        if (total) *total = tot;
+        long long wcap = std::min<long long>(cap, tot);
+        if (wcap > 0) {
+            int* dindex = nullptr;
+            const long long* doff = (const long long*)offsets;
+            ASP_TRY(device_scratch(ws.aux[kIndex], dindex, wcap * sizeof(int)));
+            ASP_TRY(to_device(ws, ws.aux[kOffsets], doff, npix * sizeof(long long), st, Copy::kPlain));
+            hipLaunchKernelGGL(k_neighbours, dim3((unsigned)npix), dim3(kBlock), 0, st, g, s, d[0], d[1],
+                               d[2], (long long)n, dpix, dcnt, doff, dindex, wcap, 1);
+            ASP_LAUNCHED();
+            ASP_TRY(to_host(index, dindex, wcap * sizeof(int), st));
+            ASP_HIP(hipStreamSynchronize(st));
+        }
+        return ASP_OK;
+    });
 }
 
 }  // extern "C"

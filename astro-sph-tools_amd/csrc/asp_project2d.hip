@@ -181,7 +181,7 @@ Grid window_grid(const Grid& full, int tx0, int tx1) {  // whole tile rows
 static bool split_scan_on() {
     if (env_set("ASP_SPLIT_SCAN")) return env_int("ASP_SPLIT_SCAN", 0) != 0;
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return false;
     SlotTable& T = g_slots[dev];
     std::lock_guard<std::mutex> lock(T.mu);
     for (int k = 1; k < kMapSlots; ++k)
@@ -533,21 +533,20 @@ int setup_grid(const MapArgs& m, Grid& g) {
 // Host outputs: device maps in the workspace (pre-loaded for ASP_F_ACCUMULATE).
 static int host_outputs(Workspace& ws, float* out0, float* out1, long long npix, int flags,
                         hipStream_t st, float*& d0, float*& d1) {
-    const int nout = out1 ? 2 : 1;
-    for (int k = 0; k < nout; ++k) ASP_TRY(ensure(ws.out[k], (size_t)npix * sizeof(float)));
-    d0 = (float*)ws.out[0].p;
-    d1 = nout == 2 ? (float*)ws.out[1].p : nullptr;
+    const size_t bytes = (size_t)npix * sizeof(float);
+    ASP_TRY(device_scratch(ws.out[0], d0, bytes));
+    if (out1) ASP_TRY(device_scratch(ws.out[1], d1, bytes));
     if (flags & ASP_F_ACCUMULATE) {
-        ASP_HIP(hipMemcpyAsync(d0, out0, npix * sizeof(float), hipMemcpyHostToDevice, st));
-        if (d1) ASP_HIP(hipMemcpyAsync(d1, out1, npix * sizeof(float), hipMemcpyHostToDevice, st));
+        ASP_HIP(hipMemcpyAsync(d0, out0, bytes, hipMemcpyHostToDevice, st));
+        if (d1) ASP_HIP(hipMemcpyAsync(d1, out1, bytes, hipMemcpyHostToDevice, st));
     }
     return ASP_OK;
 }
 
 static int host_results(float* out0, float* out1, const float* d0, const float* d1,
                         long long npix, hipStream_t st) {
-    ASP_HIP(hipMemcpyAsync(out0, d0, npix * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (out1) ASP_HIP(hipMemcpyAsync(out1, d1, npix * sizeof(float), hipMemcpyDeviceToHost, st));
+    ASP_TRY(to_host(out0, d0, npix * sizeof(float), st));
+    if (out1) ASP_TRY(to_host(out1, d1, npix * sizeof(float), st));
     ASP_HIP(hipStreamSynchronize(st));
     return ASP_OK;
 }
@@ -593,14 +592,8 @@ static int weigh_props(Workspace& ws, const Props<T>& p, const T* a0, const T* a
                        const float** xw) {
     const T *dm = p.wm, *dr = p.wr;
     if (!dev) {
-        const T* host[2] = {p.wm, p.wr};
-        for (int k = 0; k < 2; ++k) {
-            if (!host[k]) continue;
-            ASP_TRY(ensure(ws.inw[k], (size_t)n * sizeof(T)));
-            ASP_TRY(h2d_staged(ws, ws.inw[k].p, host[k], (size_t)n * sizeof(T), st));
-        }
-        dm = (const T*)ws.inw[0].p;
-        dr = p.wr ? (const T*)ws.inw[1].p : nullptr;
+        ASP_TRY(to_device(ws, ws.inw[0], dm, (size_t)n * sizeof(T), st, Copy::kPinned));
+        if (dr) ASP_TRY(to_device(ws, ws.inw[1], dr, (size_t)n * sizeof(T), st, Copy::kPinned));
     }
     const T* src[6] = {a0, a1, nullptr, nullptr, nullptr, nullptr};
     for (int j = 0; j < p.nxp; ++j) src[2 + j] = p.xprops[j];
@@ -629,20 +622,6 @@ static int check_map(const MapArgs& m, const Props<T>& p, long long n, bool arra
     return ASP_OK;
 }
 
-// The rest of a map call's prologue: the device, the workspace slot of the call's stream
-// under its lock, ordered behind the slot's previous call; body(ws, st) is the call.
-template <class F>
-static int with_workspace(const MapArgs& m, F&& body) {
-    ASP_TRY(set_device(m.device));
-    hipStream_t st = (hipStream_t)m.stream;
-    Workspace& ws = slot_ws(m.device, map_slot(m.device, st));
-    std::lock_guard<std::mutex> lock(ws.mu);
-    ASP_TRY(ws_begin(ws, st));
-    WsEnd ws_end_(ws, st);
-    ASP_TRY(body(ws, st));
-    return ws_end_.finish();
-}
-
 // xw: the fp32 arrays of properties 2.. (unused entries repeat the first)
 static XArgs extra_args(const float* const* xw, int nxp) {
     XArgs xa{};
@@ -658,7 +637,7 @@ static int project2d(const float* u, const float* v, const float* h, long long n
     const int row_lo = m.row_lo, row_hi = m.row_hi < 0 ? m.nx : m.row_hi;
     if (row_lo < 0 || row_lo >= row_hi || row_hi > m.nx)
         return fail(ASP_ERR_INVALID, "rows: need 0 <= row_lo < row_hi <= nx");
-    return with_workspace(m, [&](Workspace& ws, hipStream_t st) -> int {
+    return with_workspace(m.device, (hipStream_t)m.stream, true, [&](Workspace& ws, hipStream_t st) -> int {
         const int nout = m.out1 ? 2 : 1;
         const bool dev = m.flags & ASP_F_DEVICE_PTRS;
         // the rows this call writes (the grid keeps the whole image's)
@@ -666,16 +645,10 @@ static int project2d(const float* u, const float* v, const float* h, long long n
         const float *du = u, *dv = v, *dh = h, *da0 = p.a0, *da1 = p.a1;
         float *d0 = m.out0, *d1 = m.out1;
         if (!dev) {
-            const float* src[5] = {u, v, h, p.a0, p.a1};
-            for (int k = 0; k < 4 + (nout == 2); ++k) {
-                ASP_TRY(ensure(ws.in[k], (size_t)n * sizeof(float)));
-                ASP_TRY(h2d_staged(ws, ws.in[k].p, src[k], (size_t)n * sizeof(float), st));
-            }
-            du = (const float*)ws.in[0].p;
-            dv = (const float*)ws.in[1].p;
-            dh = (const float*)ws.in[2].p;
-            da0 = (const float*)ws.in[3].p;
-            da1 = nout == 2 ? (const float*)ws.in[4].p : nullptr;
+            const float** src[5] = {&du, &dv, &dh, &da0, &da1};
+            for (int k = 0; k < 4 + (nout == 2); ++k)
+                ASP_TRY(to_device(ws, ws.in[k], *src[k], (size_t)n * sizeof(float), st,
+                                  Copy::kPinned));
             ASP_TRY(host_outputs(ws, m.out0, m.out1, npix, m.flags, st, d0, d1));
         }
         const float* xw[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -726,7 +699,7 @@ static int project2d_f64(const double* pos, const double* h, long long n, int ax
     Grid g;
     ASP_TRY(setup_grid(m, g));
     g.mixed = cull_axis != axis;
-    return with_workspace(m, [&](Workspace& ws, hipStream_t st) -> int {
+    return with_workspace(m.device, (hipStream_t)m.stream, true, [&](Workspace& ws, hipStream_t st) -> int {
         const int nout = m.out1 ? 2 : 1;
         const bool dev = m.flags & ASP_F_DEVICE_PTRS;
         const bool dev_out = dev || (m.flags & ASP_F_DEVICE_OUTPUTS);  // maps stay on the device
@@ -735,17 +708,10 @@ static int project2d_f64(const double* pos, const double* h, long long n, int ax
         float *d0 = m.out0, *d1 = m.out1;
         if (!dev) {
             // the fp64 arrays stay resident: the exact re-decisions read positions and h
-            const double* src[4] = {pos, h, p.a0, p.a1};
-            const size_t words[4] = {3, 1, 1, 1};
-            for (int k = 0; k < 3 + (nout == 2); ++k) {
-                const size_t bytes = (size_t)n * words[k] * sizeof(double);
-                ASP_TRY(ensure(ws.in64[k], bytes));
-                ASP_TRY(h2d_staged(ws, ws.in64[k].p, src[k], bytes, st));
-            }
-            dpos = (const double*)ws.in64[0].p;
-            dh64 = (const double*)ws.in64[1].p;
-            da0 = (const double*)ws.in64[2].p;
-            da1 = nout == 2 ? (const double*)ws.in64[3].p : nullptr;
+            const double** src[4] = {&dpos, &dh64, &da0, &da1};
+            for (int k = 0; k < 3 + (nout == 2); ++k)
+                ASP_TRY(to_device(ws, ws.in64[k], *src[k], (size_t)n * (k ? 1 : 3) * sizeof(double),
+                                  st, Copy::kPinned));
             if (!dev_out) ASP_TRY(host_outputs(ws, m.out0, m.out1, npix, m.flags, st, d0, d1));
         }
         for (int k = 0; k < 4 + (nout == 2); ++k)
@@ -917,9 +883,7 @@ int asp_ratio(float* out0, const float* out1, int64_t n, int32_t device, void* s
 
 int asp_profile_stages(int32_t device, uint32_t stage_mask) {
     t_err.clear();
-    int ndev = asp_device_count();
-    if (device < 0 || device >= ndev) return fail(ASP_ERR_INVALID, "bad device");
-    ASP_HIP(hipSetDevice(device));
+    ASP_TRY(set_device(device));
     for (int sl = 0; sl < kMapSlots; ++sl) {  // every map slot's workspace
         Workspace& ws = slot_ws(device, sl);
         std::lock_guard<std::mutex> lock(ws.mu);
@@ -945,7 +909,7 @@ int asp_profile(int32_t device, int32_t enable) {
 
 int asp_profile_read(int32_t device, double* ms_sum, int64_t* launches, int32_t nstages) {
     t_err.clear();
-    if (device < 0 || device >= 64 || !ms_sum || !launches)
+    if (device < 0 || device >= kMaxDevices || !ms_sum || !launches)
         return fail(ASP_ERR_INVALID, "bad argument");
     for (int k = 0; k < nstages; ++k) {
         ms_sum[k] = 0.0;
@@ -967,26 +931,22 @@ int asp_profile_read(int32_t device, double* ms_sum, int64_t* launches, int32_t 
 }
 
 int asp_last_stats(int32_t device, int64_t* stats, int32_t nstats) {
-    if (device < 0 || device >= 64 || !stats) return fail(ASP_ERR_INVALID, "bad argument");
+    if (device < 0 || device >= kMaxDevices || !stats) return fail(ASP_ERR_INVALID, "bad argument");
     std::lock_guard<std::mutex> lk(g_ws[device].mu);  // a call in flight writes them
     for (int k = 0; k < nstats && k < kNStats; ++k) stats[k] = g_ws[device].stats[k];
     return ASP_OK;
 }
 
 int asp_release(int32_t device) {
-    int lo = device < 0 ? 0 : device, hi = device < 0 ? 63 : device;
-    int ndev = asp_device_count();
+    int lo = device < 0 ? 0 : device, hi = device < 0 ? kMaxDevices - 1 : device;
+    int ndev = std::min(asp_device_count(), kMaxDevices);
     for (int d = lo; d <= hi && d < ndev; ++d)
       for (int sl = 0; sl < kMapSlots; ++sl) {
         Workspace& ws = slot_ws(d, sl);
         std::lock_guard<std::mutex> lock(ws.mu);
         if (hipSetDevice(d) != hipSuccess) continue;
         if (ws.last_ev) (void)hipEventSynchronize(ws.last_ev);
-        for (Buf* b : ws.all_bufs()) {
-            if (b->p) (void)hipFree(b->p);
-            b->p = nullptr;
-            b->cap = 0;
-        }
+        free_buffers(ws);
         if (ws.h_counters) (void)hipHostFree(ws.h_counters);
         ws.h_counters = nullptr;
         release_pinned(ws);

@@ -1112,83 +1112,65 @@ static int project3d(const float* x, const float* y, const float* z, const float
     if (g.nb < 0)
         return fail(ASP_ERR_UNSUPPORTED, "cube slab too wide: ny x (k_hi - k_lo) spans more than "
                                          "16384 16x32 brick columns; split the planes [k_lo, k_hi)");
-    if (device < 0 || device >= 64) return fail(ASP_ERR_INVALID, "bad device");
-    int ndev = 0;
-    ASP_HIP(hipGetDeviceCount(&ndev));
-    if (device >= ndev) return fail(ASP_ERR_INVALID, "device index out of range");
-    ASP_HIP(hipSetDevice(device));
-    hipStream_t st = (hipStream_t)stream;
     // a workspace slot per stream, as the 2-D maps have (asp_host.hpp map_slot): cubes on
     // two streams overlap -- one cube's store-bound scatter beside the other's VALU-bound
     // deposit (round 5)
-    Workspace& ws = slot_ws(device, map_slot(device, st));
-    std::lock_guard<std::mutex> lock(ws.mu);
-    ASP_TRY(ws_begin(ws, st));
-    WsEnd ws_end_(ws, st);
-    const bool dev = flags & ASP_F_DEVICE_PTRS;
-    const int acc = (flags & ASP_F_ACCUMULATE) ? 1 : 0;
-    const long long nvox = (long long)nx * ny * g.nzl;
-    const float *dx = x, *dy = y, *dz = z, *dh = h, *da = a;
-    float* dout = out;
-    if (!dev) {
-        const float* src[5] = {x, y, z, h, a};
-        for (int k = 0; k < 5; ++k) {
-            ASP_TRY(ensure(ws.in[k], (size_t)n * sizeof(float)));
-            if (n > 0)
-                ASP_HIP(hipMemcpyAsync(ws.in[k].p, src[k], (size_t)n * sizeof(float),
-                                       hipMemcpyHostToDevice, st));
+    return with_workspace(device, (hipStream_t)stream, true, [&](Workspace& ws, hipStream_t st) -> int {
+        const bool dev = flags & ASP_F_DEVICE_PTRS;
+        const int acc = (flags & ASP_F_ACCUMULATE) ? 1 : 0;
+        const long long nvox = (long long)nx * ny * g.nzl;
+        const float *dx = x, *dy = y, *dz = z, *dh = h, *da = a;
+        float* dout = out;
+        if (!dev) {
+            const float** src[5] = {&dx, &dy, &dz, &dh, &da};
+            for (int k = 0; k < 5; ++k)
+                ASP_TRY(to_device(ws, ws.in[k], *src[k], (size_t)n * sizeof(float), st, Copy::kPlain));
+            ASP_TRY(device_scratch(ws.out[0], dout, (size_t)nvox * sizeof(float)));
+            if (acc)
+                ASP_HIP(hipMemcpyAsync(dout, out, nvox * sizeof(float), hipMemcpyHostToDevice, st));
         }
-        dx = (const float*)ws.in[0].p;
-        dy = (const float*)ws.in[1].p;
-        dz = (const float*)ws.in[2].p;
-        dh = (const float*)ws.in[3].p;
-        da = (const float*)ws.in[4].p;
-        ASP_TRY(ensure(ws.out[0], (size_t)nvox * sizeof(float)));
-        dout = (float*)ws.out[0].p;
-        if (acc)
-            ASP_HIP(hipMemcpyAsync(dout, out, nvox * sizeof(float), hipMemcpyHostToDevice, st));
-    }
-    if (ws.prof) ASP_TRY(prof_next(ws));
-    long long agg[4] = {0, 0, 0, 0};  // records, items, merges, slabs over the windows
-    if (n == 0) {
-        if (!acc) {
-            StageMark m(ws, kSMemset, st);
-            ASP_HIP(hipMemsetAsync(dout, 0, nvox * sizeof(float), st));
-            m.done();
+        if (ws.prof) ASP_TRY(prof_next(ws));
+        long long agg[4] = {0, 0, 0, 0};  // records, items, merges, slabs over the windows
+        if (n == 0) {
+            if (!acc) {
+                StageMark m(ws, kSMemset, st);
+                ASP_HIP(hipMemsetAsync(dout, 0, nvox * sizeof(float), st));
+                m.done();
+            }
+        } else {
+            // windows of whole brick columns in x, each <= kMaxBricks bricks: every window one
+            // pass over all particles with the footprints clipped to it; its slab of the output
+            // is contiguous ((nx, ny, nzl) C-order, x slowest)
+            const int wb = std::max(1, kMaxBricks / (g.nby * g.nbz));
+            for (int bx0 = 0; bx0 < g.nbx; bx0 += wb) {
+                Grid3 w = g;
+                w.i_lo = bx0 * kBX;
+                w.nxl = std::min((bx0 + wb) * kBX, nx) - w.i_lo;
+                w.nbx = std::min(wb, g.nbx - bx0);
+                w.nb = w.nbx * g.nby * g.nbz;
+                // particle batches (for_batches); batches after the first accumulate
+                ASP_TRY(for_batches(n, [&](long long a, long long b, int i) {
+                    return cube_pass(ws, w, dx + a, dy + a, dz + a, dh + a, da + a, b - a, kid,
+                                     i ? 1 : acc, dout + (long long)w.i_lo * ny * g.nzl, st, agg);
+                }));
+            }
         }
-    } else {
-        // windows of whole brick columns in x, each <= kMaxBricks bricks: every window one
-        // pass over all particles with the footprints clipped to it; its slab of the output
-        // is contiguous ((nx, ny, nzl) C-order, x slowest)
-        const int wb = std::max(1, kMaxBricks / (g.nby * g.nbz));
-        for (int bx0 = 0; bx0 < g.nbx; bx0 += wb) {
-            Grid3 w = g;
-            w.i_lo = bx0 * kBX;
-            w.nxl = std::min((bx0 + wb) * kBX, nx) - w.i_lo;
-            w.nbx = std::min(wb, g.nbx - bx0);
-            w.nb = w.nbx * g.nby * g.nbz;
-            // particle batches (for_batches); batches after the first accumulate
-            ASP_TRY(for_batches(n, [&](long long a, long long b, int i) {
-                return cube_pass(ws, w, dx + a, dy + a, dz + a, dh + a, da + a, b - a, kid,
-                                 i ? 1 : acc, dout + (long long)w.i_lo * ny * g.nzl, st, agg);
-            }));
+        if (!dev) {
+            ASP_TRY(to_host(out, dout, nvox * sizeof(float), st));
+            ASP_HIP(hipStreamSynchronize(st));
         }
-    }
-    if (!dev) {
-        ASP_HIP(hipMemcpyAsync(out, dout, nvox * sizeof(float), hipMemcpyDeviceToHost, st));
-        ASP_HIP(hipStreamSynchronize(st));
-    }
-    stats_clear(ws);  // (the wide count and the 2-D-only counters stay 0)
-    ws.stats[0] = agg[0];
-    ws.stats[1] = agg[1];
-    ws.stats[3] = kBrickVox;
-    ws.stats[4] = (long long)g.nbx * g.nby * g.nbz;
-    ws.stats[5] = n > 0 ? ws.h_counters[cChunk] : 0;
-    ws.stats[6] = agg[2];
-    ws.stats[7] = agg[3];
-    ws.stats[8] = n > 0 ? 1 : 0;
-    stats_publish(ws, device);
-    return ws_end_.finish();
+        stats_clear(ws);  // (the wide count and the 2-D-only counters stay 0)
+        ws.stats[0] = agg[0];
+        ws.stats[1] = agg[1];
+        ws.stats[3] = kBrickVox;
+        ws.stats[4] = (long long)g.nbx * g.nby * g.nbz;
+        ws.stats[5] = n > 0 ? ws.h_counters[cChunk] : 0;
+        ws.stats[6] = agg[2];
+        ws.stats[7] = agg[3];
+        ws.stats[8] = n > 0 ? 1 : 0;
+        stats_publish(ws, device);
+        return ASP_OK;
+    });
 }
 
 }  // namespace asp

@@ -236,64 +236,62 @@ static int stage_particles(const double* pos, const double* h, const double* a0,
     for (int k = 0; k < 3; ++k) S.s[k] = centre ? centre[k] : 0.0;
     S.images = images;
     S.lo = S.centred ? -(box_width / 2) : 0.0;
-    ASP_TRY(set_device(device));
-    Workspace& ws = g_ws[device];
-    std::lock_guard<std::mutex> lock(ws.mu);
-    ASP_TRY(ws_begin(ws, st));
-    WsEnd ws_end_(ws, st);
-    ASP_TRY(ensure(ws.aux[kAuxCounters], 2 * sizeof(unsigned long long)));
-    unsigned long long* dimg = (unsigned long long*)ws.aux[kAuxCounters].p;
-    ASP_HIP(hipMemsetAsync(dimg, 0, 2 * sizeof(unsigned long long), st));
-    if ((flags & ASP_F_DEVICE_PTRS) || n == 0) {
-        if (n > 0) {
-            hipLaunchKernelGGL(k_stage, dim3(grid_for(n)), dim3(kStageBlock), 0, st, S, pos, h, a0,
-                               a1, 0LL, n, n, u, v, hf, a0f, a1f, cap, dimg);
-            ASP_HIP(hipGetLastError());
+    return with_workspace(device, st, false, [&](Workspace& ws, hipStream_t st) -> int {
+        unsigned long long* dimg = nullptr;
+        ASP_TRY(device_scratch(ws.aux[kAuxCounters], dimg, 2 * sizeof(unsigned long long)));
+        ASP_HIP(hipMemsetAsync(dimg, 0, 2 * sizeof(unsigned long long), st));
+        if ((flags & ASP_F_DEVICE_PTRS) || n == 0) {
+            if (n > 0) {
+                hipLaunchKernelGGL(k_stage, dim3(grid_for(n)), dim3(kStageBlock), 0, st, S, pos, h, a0,
+                                   a1, 0LL, n, n, u, v, hf, a0f, a1f, cap, dimg);
+                ASP_LAUNCHED();
+            }
+        } else {
+            // Host arrays: chunks copied (pinned bounce buffers) into two device staging sets
+            // alternately (stream st, side stream): the copy of chunk c + 1 overlaps the
+            // conversion of chunk c.
+            ASP_TRY(ensure_side(ws));
+            const long long C = std::min<long long>(kStageChunk, n);
+            enum { kSet = 0 };  // per-call scratch: the two staging sets, aux[kSet + 0 / 1]
+            for (int s = 0; s < 2; ++s)  // (each whole: a chunk's arrays share its set)
+                ASP_TRY(ensure(ws.aux[kSet + s], (size_t)C * 6 * sizeof(double)));
+            hipStream_t ss[2] = {st, ws.side};
+            ASP_HIP(hipEventRecord(ws.scan_ev, st));
+            ASP_HIP(hipStreamWaitEvent(ws.side, ws.scan_ev, 0));  // behind the counter reset
+            int c = 0;
+            for (long long i0 = 0; i0 < n; i0 += C, ++c) {
+                const long long m = std::min(C, n - i0);
+                hipStream_t s = ss[c & 1];
+                // the set: positions (3 C), then h, a0 and a1 (C each; those given)
+                Buf& set = ws.aux[kSet + (c & 1)];
+                const double* src[4] = {pos + 3 * i0, h ? h + i0 : nullptr, a0 ? a0 + i0 : nullptr,
+                                        a1 ? a1 + i0 : nullptr};
+                for (int k = 0; k < 4; ++k)
+                    if (src[k])
+                        ASP_TRY(to_device(ws, set, src[k], (size_t)m * (k ? 1 : 3) * sizeof(double), s,
+                                          Copy::kPinned, (size_t)C * (k ? k + 2 : 0) * sizeof(double)));
+                hipLaunchKernelGGL(k_stage, dim3(grid_for(m)), dim3(kStageBlock), 0, s, S, src[0], src[1],
+                                   src[2], src[3], i0, i0 + m, n, u, v, hf, a0f, a1f, cap, dimg);
+                ASP_LAUNCHED();
+            }
+            ASP_HIP(hipEventRecord(ws.done_ev, ws.side));
+            ASP_HIP(hipStreamWaitEvent(st, ws.done_ev, 0));
         }
-    } else {
-        // Host arrays: chunks copied (pinned bounce buffers) into two device staging sets
-        // alternately (stream st, side stream): the copy of chunk c + 1 overlaps the
-        // conversion of chunk c.
-        ASP_TRY(ensure_side(ws));
-        const long long C = std::min<long long>(kStageChunk, n);
-        enum { kSet = 0 };  // per-call scratch: the two staging sets, aux[kSet + 0 / 1]
-        for (int s = 0; s < 2; ++s)
-            ASP_TRY(ensure(ws.aux[kSet + s], (size_t)C * 6 * sizeof(double)));
-        hipStream_t ss[2] = {st, ws.side};
-        ASP_HIP(hipEventRecord(ws.scan_ev, st));
-        ASP_HIP(hipStreamWaitEvent(ws.side, ws.scan_ev, 0));  // behind the counter reset
-        int c = 0;
-        for (long long i0 = 0; i0 < n; i0 += C, ++c) {
-            const long long m = std::min(C, n - i0);
-            hipStream_t s = ss[c & 1];
-            double* d = (double*)ws.aux[kSet + (c & 1)].p;
-            double *dp = d, *dh = d + 3 * C, *d0 = d + 4 * C, *d1 = d + 5 * C;
-            ASP_TRY(h2d_staged(ws, dp, pos + 3 * i0, (size_t)m * 3 * sizeof(double), s));
-            if (h) ASP_TRY(h2d_staged(ws, dh, h + i0, (size_t)m * sizeof(double), s));
-            if (a0) ASP_TRY(h2d_staged(ws, d0, a0 + i0, (size_t)m * sizeof(double), s));
-            if (a1) ASP_TRY(h2d_staged(ws, d1, a1 + i0, (size_t)m * sizeof(double), s));
-            hipLaunchKernelGGL(k_stage, dim3(grid_for(m)), dim3(kStageBlock), 0, s, S, dp,
-                               h ? dh : nullptr, a0 ? d0 : nullptr, a1 ? d1 : nullptr, i0, i0 + m,
-                               n, u, v, hf, a0f, a1f, cap, dimg);
-            ASP_HIP(hipGetLastError());
-        }
-        ASP_HIP(hipEventRecord(ws.done_ev, ws.side));
-        ASP_HIP(hipStreamWaitEvent(st, ws.done_ev, 0));
-    }
-    unsigned long long nimg[2] = {0, 0};
-    ASP_HIP(hipMemcpyAsync(nimg, dimg, sizeof(nimg), hipMemcpyDeviceToHost, st));
-    ASP_HIP(hipStreamSynchronize(st));
-    ASP_TRY(ws_end_.finish());
-    if (nimg[1])
-        return fail(ASP_ERR_UNSUPPORTED, std::to_string(nimg[1]) + " particles reach beyond " +
-                                             std::to_string(kMaxImageShift) +
-                                             " box widths (2|h| > 3 L): periodic images unsupported");
-    *n_out = n + (long long)nimg[0];
-    if (*n_out > cap)
-        return fail(ASP_ERR_INVALID, "periodic images exceed the output capacity (" +
-                                         std::to_string(*n_out) + " > " + std::to_string(cap) +
-                                         "); n_out holds the size needed");
-    return ASP_OK;
+        unsigned long long nimg[2] = {0, 0};
+        ASP_TRY(to_host(nimg, dimg, sizeof(nimg), st));
+        ASP_HIP(hipStreamSynchronize(st));
+        // (the errors below leave through WsEnd: the end event is recorded all the same)
+        if (nimg[1])
+            return fail(ASP_ERR_UNSUPPORTED, std::to_string(nimg[1]) + " particles reach beyond " +
+                                                 std::to_string(kMaxImageShift) +
+                                                 " box widths (2|h| > 3 L): periodic images unsupported");
+        *n_out = n + (long long)nimg[0];
+        if (*n_out > cap)
+            return fail(ASP_ERR_INVALID, "periodic images exceed the output capacity (" +
+                                             std::to_string(*n_out) + " > " + std::to_string(cap) +
+                                             "); n_out holds the size needed");
+        return ASP_OK;
+    });
 }
 
 // ----------------------------------------------------------------------------------
@@ -367,7 +365,7 @@ int stage_device(const double* pos, const double* h, const double* a0, const dou
     S.b = cols[axis][1];
     hipLaunchKernelGGL(k_stage, dim3(grid_for(n)), dim3(kStageBlock), 0, st, S, pos, h, a0, a1,
                        0LL, n, n, u, v, hf, a0f, a1f, n, (unsigned long long*)nullptr);
-    ASP_HIP(hipGetLastError());
+    ASP_LAUNCHED();
     return ASP_OK;
 }
 
@@ -404,7 +402,7 @@ int asp_periodic(int32_t op, const double* a, int64_t pa, const double* b, int64
     hipLaunchKernelGGL(k_periodic, dim3(grid_for(n)), dim3(kStageBlock), 0, (hipStream_t)stream,
                        (int)op, a, (long long)pa, b, (long long)(op == ASP_PB_WRAP ? 1 : pb),
                        (long long)n, box_width, (int)(origin_is_centre != 0), out);
-    ASP_HIP(hipGetLastError());
+    ASP_LAUNCHED();
     return ASP_OK;
 }
 
@@ -419,7 +417,7 @@ int asp_wrapped_distance(const double* from, int64_t pf, const double* to, int64
     hipLaunchKernelGGL(k_wrapped_distance, dim3(grid_for(rows)), dim3(kStageBlock), 0,
                        (hipStream_t)stream, from, (long long)pf, to, (long long)pt,
                        (long long)rows, box_width, (int)(squared != 0), out);
-    ASP_HIP(hipGetLastError());
+    ASP_LAUNCHED();
     return ASP_OK;
 }
 

@@ -332,10 +332,7 @@ extern "C" int asp_table_interp3(const double* table, int32_t n0, int32_t n1, in
     if (n == 0) return ASP_OK;
     if (!table || !g0 || !g1 || !g2 || !points || !out || (mode && (!a0 || !a1)))
         return fail(ASP_ERR_INVALID, "NULL array");
-    int ndev = 0;
-    ASP_HIP(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(ASP_ERR_INVALID, "bad device");
-    ASP_HIP(hipSetDevice(device));
+    ASP_TRY(set_device(device));
     TabAxes A{{g0, g1, g2}, {n0, n1, n2}};
     const bool lds = (long long)n0 + n1 + n2 <= kTabLdsAxis;
     const dim3 grid((unsigned)((n + kTabBlock * kTabPerThread - 1) / (kTabBlock * kTabPerThread)));
@@ -353,7 +350,7 @@ extern "C" int asp_table_interp3(const double* table, int32_t n0, int32_t n1, in
         if (lds) hipLaunchKernelGGL((k_table<2, true>), grid, dim3(kTabBlock), 0, st, table, A, points, (int)zaxis, zvalue, (long long)n, fill, (int)mode, a0, a1, out);
         else hipLaunchKernelGGL((k_table<2, false>), grid, dim3(kTabBlock), 0, st, table, A, points, (int)zaxis, zvalue, (long long)n, fill, (int)mode, a0, a1, out);
     }
-    ASP_HIP(hipGetLastError());
+    ASP_LAUNCHED();
     return ASP_OK;
 }
 
@@ -373,10 +370,7 @@ extern "C" int asp_table_interp(const double* table, int32_t ndim, const int32_t
     if (n < 0) return fail(ASP_ERR_INVALID, "n < 0");
     if (n == 0) return ASP_OK;
     if (!table || !points || !out || (mode && (!a0 || !a1))) return fail(ASP_ERR_INVALID, "NULL array");
-    int ndev = 0;
-    ASP_HIP(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(ASP_ERR_INVALID, "bad device");
-    ASP_HIP(hipSetDevice(device));
+    ASP_TRY(set_device(device));
     TabND A{};
     long long st = 1;
     for (int d = ndim - 1; d >= 0; --d) {
@@ -403,6 +397,6 @@ extern "C" int asp_table_interp(const double* table, int32_t ndim, const int32_t
         ASP_TAB_ND(6)
     }
 #undef ASP_TAB_ND
-    ASP_HIP(hipGetLastError());
+    ASP_LAUNCHED();
     return ASP_OK;
 }

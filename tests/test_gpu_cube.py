@@ -126,6 +126,27 @@ def test_cube_device_api_accumulate(gpu):
     assert torch.allclose(c3, c1, rtol=1e-5, atol=1e-6 * float(c1.abs().max()))
 
 
+def test_cube_host_arrays_accumulate(gpu, oracle):
+    """asp_project3d from host arrays: the cube against the oracle, and ASP_F_ACCUMULATE on a
+    host cube (pre-loaded into the workspace, summed, copied back) doubling it."""
+    from asp_amd import _lib
+    size = (24, 20, 36)  # several bricks on every axis, none whole
+    x, y, z, h, m = _plummer(300, 9, size)
+    arrs = [np.ascontiguousarray(a, np.float32) for a in (x, y, z, h, m)]
+
+    def call(out, flags):
+        _lib.check(_lib.lib().asp_project3d(*(_lib.ptr(a) for a in arrs), h.size, *EXT, *size, 0,
+                                            size[2], _lib.ASP_KERNEL_CUBIC_SPLINE, flags,
+                                            _lib.ptr(out), 0, None))
+        return out
+
+    c1 = call(np.full(size, np.nan, np.float32), 0)
+    assert_map_close(c1.astype(np.float64), oracle.project3d(x, y, z, h, m, size, EXT))
+    c2 = call(c1.copy(), _lib.ASP_F_ACCUMULATE)
+    assert np.count_nonzero(c1) > 0
+    np.testing.assert_allclose(c2, 2 * c1, rtol=1e-6, atol=0)
+
+
 def test_cube_record_placement_trials(gpu, oracle, monkeypatch):
     """The placement trials of a fresh record buffer (the probe scatter run into several
     candidate buffers, the fastest kept holding the call's records) leave the voxel counts

@@ -70,6 +70,23 @@ def test_g1_kernel_eval_on_device(gpu):
         quartic_spline_kernel(g["r"].astype(np.float32), g["h"])
 
 
+def test_g1_kernel_eval_device_pointers(gpu):
+    """asp_kernel_eval on device arrays (ASP_F_DEVICE_PTRS): the same values."""
+    import torch
+    from asp_amd import _lib
+    g = golden("g1_kernel_table.npz")
+    r, h = (torch.from_numpy(np.ascontiguousarray(g[k], np.float64)).cuda() for k in ("r", "h"))
+    w = torch.full_like(r, float("nan"))
+    d = _lib._d
+    _lib.check(_lib.lib().asp_kernel_eval(_lib.ASP_KERNEL_CUBIC_SPLINE, _lib.ptr(r, d),
+                                          _lib.ptr(h, d), _lib.ptr(w, d), r.numel(),
+                                          _lib.ASP_F_DEVICE_PTRS, 0, None))
+    torch.cuda.synchronize()
+    w = w.cpu().numpy()
+    assert np.array_equal(w == 0, g["w"] == 0)
+    np.testing.assert_allclose(w, g["w"], rtol=4e-16 * 8, atol=0)
+
+
 @pytest.mark.parametrize("case", list(range(11)))
 def test_g2_hand_cases(gpu, case):
     from asp_amd.tools.projections import create_image
@@ -117,7 +134,12 @@ def test_g4_chunk_membership_bitexact(gpu):
     _lib.check(_lib.lib().asp_chunk_ranges(_lib.ptr(u), _lib.ptr(v), _lib.ptr(hh), u.size,
                                            *map(float, ext), size[0], size[1], cs,
                                            *[_lib.ptr(o, _lib._i32) for o in out], 0, 0, None))
-    cx0, cx1, cy0, cy1 = out
+    assert_chunk_membership(out, g)
+    del C
+
+
+def assert_chunk_membership(ranges, g):
+    cx0, cx1, cy0, cy1 = ranges
     ncx, ncy = g["n_chunks"]
     offs = g["offsets"]
     for cx in range(ncx):
@@ -125,7 +147,22 @@ def test_g4_chunk_membership_bitexact(gpu):
             k = cx * ncy + cy
             got = np.nonzero((cx0 <= cx) & (cx <= cx1) & (cy0 <= cy) & (cy <= cy1))[0]
             assert np.array_equal(got, g["index"][offs[k]:offs[k + 1]]), (cx, cy)
-    del C
+
+
+def test_g4_chunk_membership_device_pointers(gpu):
+    """asp_chunk_ranges on device arrays (ASP_F_DEVICE_PTRS): the same membership."""
+    import torch
+    from asp_amd import _lib
+    pos, h, A, size, cs, ext, _ = g3()
+    u, v, hh = (torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
+                for a in (pos[:, 0], pos[:, 1], h))
+    out = [torch.full((u.numel(),), -7, dtype=torch.int32, device="cuda:0") for _ in range(4)]
+    _lib.check(_lib.lib().asp_chunk_ranges(_lib.ptr(u), _lib.ptr(v), _lib.ptr(hh), u.numel(),
+                                           *map(float, ext), size[0], size[1], cs,
+                                           *[_lib.ptr(o, _lib._i32) for o in out],
+                                           _lib.ASP_F_DEVICE_PTRS, 0, None))
+    torch.cuda.synchronize()
+    assert_chunk_membership([o.cpu().numpy() for o in out], golden("g4_tile_membership.npz"))
 
 
 def gpu_neighbours(u, v, h, ext, size, cs, pixels):

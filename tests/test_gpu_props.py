@@ -181,3 +181,42 @@ def test_sph_f64_host_arrays_through_the_c_abi(gpu, oracle):
         want, _ = oracle.project_scatter(pos[:, 0], pos[:, 1], h, A * w, None, G, 32, *ext,
                                          kernel="cubic")
         assert_map_close(img, want)
+
+
+def test_fp32_host_arrays_through_the_c_abi(gpu, oracle):
+    """asp_project2d and asp_project2d_sph on HOST float32 arrays (no device pointers: the
+    particle arrays, the weights and the maps staged by the library): both maps against the
+    oracle; ASP_F_ACCUMULATE on host maps (pre-loaded into the workspace) doubles them."""
+    from asp_amd import _lib
+    from test_gpu_parity import assert_map_close
+    L, P = _lib.lib(), _lib.ptr
+    rng = np.random.default_rng(17)
+    n, G, ext = 400, (96, 80), (-1.5, 1.5, -1.5, 1.5)  # 2 x 2 tiles, none whole
+    f32 = lambda a: np.ascontiguousarray(a, np.float32)  # noqa: E731
+    x, y = f32(rng.normal(0, 0.5, n)), f32(rng.normal(0, 0.5, n))
+    h, A = f32(rng.uniform(0.02, 0.3, n)), f32(rng.uniform(1.0, 10.0, n))
+    B = f32(rng.uniform(0.5, 2.0, n))
+    m, rho = f32(rng.uniform(0.5, 2.0, n)), f32(np.exp(rng.uniform(-3, 3, n)))
+    d64 = lambda a: a.astype(np.float64)  # noqa: E731
+    tail = (n, *ext, G[0], G[1], 32, _lib.ASP_KERNEL_CUBIC_SPLINE)
+    o0, o1 = np.full(G, np.nan, np.float32), np.full(G, np.nan, np.float32)
+    _lib.check(L.asp_project2d(P(x), P(y), P(h), P(A), P(B), *tail, 0, P(o0), P(o1), 0, None))
+    w0, w1 = oracle.project_scatter(d64(x), d64(y), d64(h), d64(A), d64(B), G, 32, *ext,
+                                    kernel="cubic")
+    assert_map_close(o0, w0)
+    assert_map_close(o1, w1)
+    s0, s1 = o0.copy(), o1.copy()
+    _lib.check(L.asp_project2d(P(x), P(y), P(h), P(A), P(B), *tail, _lib.ASP_F_ACCUMULATE, P(s0),
+                               P(s1), 0, None))
+    assert np.count_nonzero(o0) > 0
+    np.testing.assert_allclose(s0, 2 * o0, rtol=1e-6, atol=0)
+    np.testing.assert_allclose(s1, 2 * o1, rtol=1e-6, atol=0)
+    for dens in (rho, None):
+        img = np.full(G, np.nan, np.float32)
+        props, outs = (_lib._f * 1)(P(A)), (_lib._f * 1)(P(img))
+        _lib.check(L.asp_project2d_sph(P(x), P(y), P(h), P(m), P(dens), props, 1, *tail, 0, outs,
+                                       0, None))
+        w = d64(m) / d64(dens) if dens is not None else d64(m)
+        want, _ = oracle.project_scatter(d64(x), d64(y), d64(h), d64(A) * w, None, G, 32, *ext,
+                                         kernel="cubic")
+        assert_map_close(img, want)
