@@ -16,6 +16,8 @@ LIB_PATH = os.environ.get("ASP_LIB", os.path.join(ROOT, "lib", "libasp_hip.so"))
 ASP_KERNEL_CUBIC_SPLINE = 0
 ASP_KERNEL_WENDLAND_C2 = 1
 ASP_KERNEL_INDICATOR = 2
+ASP_KERNEL_CUBIC_SPLINE_COLUMN = 3
+ASP_KERNEL_WENDLAND_C2_COLUMN = 4
 
 ASP_F_DEVICE_PTRS = 0x1
 ASP_F_RATIO = 0x2

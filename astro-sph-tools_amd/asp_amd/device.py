@@ -9,7 +9,9 @@ from . import _lib
 
 _KERNEL_NAMES = {"cubic": _lib.ASP_KERNEL_CUBIC_SPLINE, "quartic_spline_kernel": 0,
                  "cubic_spline": 0, "wendland_c2": _lib.ASP_KERNEL_WENDLAND_C2,
-                 "indicator": _lib.ASP_KERNEL_INDICATOR}
+                 "indicator": _lib.ASP_KERNEL_INDICATOR,
+                 "cubic_column": _lib.ASP_KERNEL_CUBIC_SPLINE_COLUMN,
+                 "wendland_c2_column": _lib.ASP_KERNEL_WENDLAND_C2_COLUMN}
 
 
 def kernel_id(kernel) -> int:

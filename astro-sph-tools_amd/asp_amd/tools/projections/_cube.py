@@ -20,7 +20,7 @@ from __future__ import annotations
 import numpy as np
 
 from ... import _lib
-from ._kernels import native_kernel_id, quartic_spline_kernel
+from ._kernels import COLUMN_KERNEL_IDS, native_kernel_id, quartic_spline_kernel
 
 
 def create_cube(positions: np.ndarray, smoothing_lengths: np.ndarray,
@@ -39,6 +39,10 @@ def create_cube(positions: np.ndarray, smoothing_lengths: np.ndarray,
         raise ValueError(f"positions ({n}), smoothing_lengths ({h.shape[0]}) and "
                          f"particle_properties ({A.shape[0]}) differ in length")
     kid = native_kernel_id(kernel_func)
+    if kid in COLUMN_KERNEL_IDS:
+        raise ValueError(f"{kernel_func!r} is a column-integrated kernel: it has no 3-D form, "
+                         "a cube takes quartic_spline_kernel, wendland_c2_kernel or "
+                         "indicator_kernel")
     nx, ny, nz = (int(c) for c in cube_size)
     k_lo, k_hi = (0, nz) if planes is None else (int(planes[0]), int(planes[1]))
     if min(nx, ny, nz) <= 0 or k_hi <= k_lo:

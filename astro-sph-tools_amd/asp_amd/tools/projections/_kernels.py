@@ -4,6 +4,8 @@ Mirrors ``quartic_spline_kernel`` (/root/reference/src/astro_sph_tools/tools/pro
 _kernels.pyx:9-20): ``W(r, h)`` over two 1-D float64 arrays, returning a new float64
 array, evaluated ON THE GPU (asp_kernel_eval).  Despite its name the reference kernel is
 the M4 cubic spline with support 2h and 3-D normalisation 1/(pi h^3); that is kept.
+The two ``*_column_kernel`` objects are those kernels integrated along the line of sight
+(2-D normalisation 1/h^2): maps made with them are column densities and conserve sum A.
 
 The kernel objects also carry the C-ABI kernel id, which is how ``create_image``
 recognises them and runs the whole projection natively.  Any other callable (the
@@ -69,7 +71,22 @@ indicator_kernel = SPHKernel(
     "W = 1 for every pair inside 2h: create_image with this kernel and A = 1 counts the "
     "neighbours of every pixel (neighbour-set verification).")
 
-KERNELS = {k.kernel_id: k for k in (quartic_spline_kernel, wendland_c2_kernel, indicator_kernel)}
+cubic_spline_column_kernel = SPHKernel(
+    "cubic_spline_column_kernel", _lib.ASP_KERNEL_CUBIC_SPLINE_COLUMN,
+    "M4 cubic spline integrated along the line of sight: W_col(r, h) = F(q) / (pi h^2), "
+    "F(q) = 2 int_0^sqrt(4-q^2) w(sqrt(q^2+z^2)) dz with w the cubic spline's shape and "
+    "q = r/h the projected distance; 3/(2 pi h^2) at q = 0, 0 for q >= 2, "
+    "2 pi int W_col r dr = 1.  A map of A is the column density of A.")
+
+wendland_c2_column_kernel = SPHKernel(
+    "wendland_c2_column_kernel", _lib.ASP_KERNEL_WENDLAND_C2_COLUMN,
+    "Wendland C2 integrated along the line of sight: W_col(r, h) = 21 F(q) / (16 pi h^2), "
+    "F the same integral over (1-r/2)^4 (1+2r); 7/(4 pi h^2) at q = 0, 0 for q >= 2, "
+    "2 pi int W_col r dr = 1.")
+
+KERNELS = {k.kernel_id: k for k in (quartic_spline_kernel, wendland_c2_kernel, indicator_kernel,
+                                    cubic_spline_column_kernel, wendland_c2_column_kernel)}
+COLUMN_KERNEL_IDS = (_lib.ASP_KERNEL_CUBIC_SPLINE_COLUMN, _lib.ASP_KERNEL_WENDLAND_C2_COLUMN)
 
 
 def kernel_id_of(kernel_func):
@@ -88,6 +105,7 @@ def native_kernel_id(kernel_func) -> int:
     kid = kernel_id_of(kernel_func)
     if kid is None:
         raise TypeError(f"kernel_func {kernel_func!r} cannot run on the GPU here; use "
-                        "quartic_spline_kernel, wendland_c2_kernel or indicator_kernel "
+                        "quartic_spline_kernel, wendland_c2_kernel, indicator_kernel, "
+                        "cubic_spline_column_kernel or wendland_c2_column_kernel "
                         "(create_image accepts any callable)")
     return kid

@@ -26,6 +26,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "asp_column_coef.hpp"
+
 namespace asp {
 
 constexpr int kBlock = 256;        // threads per workgroup for streaming kernels
@@ -265,10 +267,23 @@ __device__ __forceinline__ bool footprint(const Grid& g, const Src64& s, int p, 
     return true;
 }
 
-// Kernel normalisation K / h^3 (fp64 for exponent range).
+// Column-integrated kernels (ids 3, 4): W_col = norm(h) f(q) with q the
+// PROJECTED distance, f the line-of-sight integral of the cubic / Wendland C2 shape
+// normalised to f(0) = 1, and norm = K F(0) / h^2.
+template <int KID>
+constexpr bool kColumn = KID == 3 || KID == 4;
+
+// Kernel normalisation K / h^3, or K F(0) / h^2 for the column kernels (fp64 for exponent
+// range).
 template <int KID>
 __device__ __forceinline__ double kernel_norm64(float h) {
     double hd = (double)h;
+    if constexpr (kColumn<KID>) {
+        double h2 = hd * hd;
+        double r = __builtin_amdgcn_rcp(h2);  // as below: reciprocal + one Newton step
+        r = r * (2.0 - h2 * r);
+        return (KID == 3 ? 3.0 / (2.0 * M_PI) : 7.0 / (4.0 * M_PI)) * r;
+    }
     double h3 = hd * hd * hd;
     // 1/h^3: hardware reciprocal + one Newton step (a few ulp; the value path is held to
     // the fp32 tolerance).  Deterministic, so the fixed-point bound of K3 stays exact.
@@ -286,12 +301,41 @@ __device__ __forceinline__ double term_coef(float a, float h) {
     return (double)a * kernel_norm64<KID>(h);
 }
 
-// Kernel shape f(q), W = norm(h) * f(q); max f = f(0) = 1 for all three kernels.
+// The column shapes' fitted form (tools/fit_column_kernels.py writes the tables,
+// asp_column_coef.hpp): with qh = min(q/2, 1), t = 1 - qh, s = sqrt(1 - qh^2)
+// (s^2 = 1 - q^2/4 = t (1 + qh)),
+//     f = t^m s P_seg(x),  m = 3 (cubic) / 4 (Wendland),  seg = min(int(32 qh), 31),
+//     x = 32 qh - seg in [0, 1],
+// P_seg a cubic by Horner.  t^m s carries the edge behaviour (f ~ (1 - q/2)^(m + 1/2)), so
+// the polynomial fits the smooth f / (t^m s) = (f / s^(2m+1)) (1 + qh)^m, and the form is a
+// product of non-negative factors that starts with t^2 -- which the edge form takes from
+// pk_square_dead.  The row of segment seg is ONE 16-byte load from the table in global
+// memory (512 bytes per kernel, resident in the vector L1): the deposits are LDS-bound, so
+// the table is kept out of LDS.  seg is clamped into [0, 31] whatever q is (NaN included).
+template <int KID>
+__device__ __forceinline__ float column_poly(float y) {  // y = 32 qh in [0, 32]
+    static_assert(kColDeg == 3 && kColRow == 4, "one float4 row per segment");
+    const int seg = min(max((int)y, 0), kColSeg - 1);
+    const float x = y - (float)seg;
+    const float4 c = *(const float4*)(KID == 3 ? kColCubic[seg] : kColWendland[seg]);
+    return fmaf(fmaf(fmaf(c.x, x, c.y), x, c.z), x, c.w);
+}
+
+// Kernel shape f(q), W = norm(h) * f(q); max f = f(0) = 1 for every kernel (the fitted
+// column forms are clamped to it: the fixed-point scale relies on |term| <= |c|).
 // Explicit FMAs: the value path is held to the fp32 tolerance, not to bit-exactness
 // (only the neighbour decision is, and it never reaches here).
 template <int KID>
 __device__ __forceinline__ float kernel_shape(float q) {
-    if constexpr (KID == 0) {  // M4 cubic spline (_kernels.pyx:14-19)
+    if constexpr (kColumn<KID>) {
+        const float qh = fminf(0.5f * q, 1.0f);
+        const float t = 1.0f - qh;
+        const float P = column_poly<KID>((float)kColSeg * qh);
+        const float s = __builtin_amdgcn_sqrtf(fmaf(-qh, qh, 1.0f));  // qh <= 1: never < 0
+        const float t2 = t * t;
+        const float rest = (KID == 3 ? t : t2) * s;
+        return fminf(t2 * (rest * P), 1.0f);
+    } else if constexpr (KID == 0) {  // M4 cubic spline (_kernels.pyx:14-19)
         float q2 = q * q;
         float a = fmaf(q2, fmaf(0.75f, q, -1.5f), 1.0f);  // 1 - 1.5 q^2 + 0.75 q^3
         float t = 2.0f - q;
@@ -443,6 +487,17 @@ __device__ __forceinline__ f2 pk_one_minus_half_clamp(f2 q) {
     asm("s_nop 0\n\tv_pk_fma_f32 %0, %1, -0.5, 1.0 op_sel_hi:[1,0,0] clamp" : "=v"(d) : "v"(q));
     return d;
 }
+// clamp(q/2, 0, 1) (a NaN gives 0), for the column forms.
+__device__ __forceinline__ f2 pk_half_clamp(f2 q) {
+    f2 d;
+    asm("s_nop 0\n\tv_pk_mul_f32 %0, %1, 0.5 op_sel_hi:[1,0] clamp" : "=v"(d) : "v"(q));
+    return d;
+}
+__device__ __forceinline__ f2 pk_mul_clamp(f2 a, f2 b) {  // clamp(a b, 0, 1)
+    f2 d;
+    asm("v_pk_mul_f32 %0, %1, %2 clamp" : "=v"(d) : "v"(a), "v"(b));
+    return d;
+}
 __device__ __forceinline__ f2 pk_one_minus_clamp(f2 q) {
     f2 d;
     asm("s_nop 0\n\tv_pk_fma_f32 %0, %1, -1.0, 1.0 op_sel_hi:[1,0,0] clamp" : "=v"(d) : "v"(q));
@@ -481,8 +536,26 @@ __device__ __forceinline__ float edge_dead2(float lo, float hi) {
     return tau < 0x1p-4f ? -(tau * tau) : 0.0f;
 }
 
+// The rest of a column form on two lanes: f = clamp(t2 (rest P)), every factor finite and
+// non-negative for qh in [0, 1]; t2 = t^2 comes from the caller (plain, or with the dead
+// zone: then a pixel inside it gets exactly 0).
+template <int KID>
+__device__ __forceinline__ f2 column_shape2(f2 qh, f2 t, f2 t2) {
+    const f2 y = qh * (float)kColSeg;
+    const f2 P = {column_poly<KID>(y.x), column_poly<KID>(y.y)};
+    const f2 s2 = __builtin_elementwise_fma(-qh, qh, (f2){1.0f, 1.0f});
+    const f2 s = {__builtin_amdgcn_sqrtf(s2.x), __builtin_amdgcn_sqrtf(s2.y)};
+    const f2 rest = (KID == 3 ? t : t2) * s;
+    return pk_mul_clamp(t2, rest * P);
+}
+
 template <int KID, bool UNIFORM = false>
 __device__ __forceinline__ f2 edge_shape2(f2 q, f2 nt2) {
+    if constexpr (kColumn<KID>) {
+        const f2 qh = pk_half_clamp(q);
+        const f2 t = (f2){1.0f, 1.0f} - qh;  // = clamp(1 - q/2): q/2 is exact
+        return column_shape2<KID>(qh, t, pk_square_dead<UNIFORM>(t, nt2));
+    }
     const f2 t = pk_one_minus_half_clamp(q);
     const f2 t2 = pk_square_dead<UNIFORM>(t, nt2);
     if constexpr (KID == 0) {

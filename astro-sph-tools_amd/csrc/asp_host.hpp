@@ -57,7 +57,8 @@ template <int V>
 using Int = std::integral_constant<int, V>;
 template <class F>
 inline int dispatch_kid(int kid, F&& f) {
-    return kid == 0 ? f(Int<0>{}) : kid == 1 ? f(Int<1>{}) : f(Int<2>{});
+    return kid == 0 ? f(Int<0>{}) : kid == 1 ? f(Int<1>{}) : kid == 2 ? f(Int<2>{})
+         : kid == 3 ? f(Int<3>{}) : f(Int<4>{});
 }
 template <class F>
 inline int dispatch(int kid, int nout, bool det, F&& f) {

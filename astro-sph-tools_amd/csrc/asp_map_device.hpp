@@ -160,7 +160,11 @@ __device__ __forceinline__ f2v fma2(f2v a, f2v b, f2v c) {  // v_pk_fma_f32
 // few ulp over 2 gives a term ~1e-28 of the peak).
 template <int KID>
 __device__ __forceinline__ f2v kernel_shape2(f2v q) {
-    if constexpr (KID == 0) {
+    if constexpr (kColumn<KID>) {  // (the clamp keeps the table index in range for any q)
+        const f2v qh = pk_half_clamp(q);
+        const f2v t = f2v{1.0f, 1.0f} - qh;
+        return column_shape2<KID>(qh, t, t * t);
+    } else if constexpr (KID == 0) {
         f2v q2 = q * q;
         f2v a = fma2(q2, fma2(q, f2v{0.75f, 0.75f}, f2v{-1.5f, -1.5f}), f2v{1.0f, 1.0f});
         f2v t = f2v{2.0f, 2.0f} - q;

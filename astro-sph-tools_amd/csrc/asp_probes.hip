@@ -19,13 +19,55 @@ namespace asp {
 // ----------------------------------------------------------------------------------
 // Auxiliary entry points: kernel evaluation, chunk ranges, neighbour lists.
 // ----------------------------------------------------------------------------------
+// Column-integrated kernels in closed form (fp64).  w(r) is a polynomial in r on each
+// piece, and with R = sqrt(q^2 + Z^2)
+//   J_n(Z) = int_0^Z r^n dz = (Z R^n + n q^2 J_{n-2}(Z)) / (n + 1),  J_0 = Z,
+//   q^2 J_{-1} = q^2 log((Z + R) / q)  (0 at q = 0),
+// so int_0^Z w dz = sum_n c[n] J_n(Z).
+template <int N>
+__device__ double column_piece(const double (&c)[N], double q, double Z) {
+    const double q2 = q * q, R = sqrt(q2 + Z * Z);
+    double J[N];
+    J[0] = Z;
+    J[1] = 0.5 * (Z * R + (q > 0.0 ? q2 * log((Z + R) / q) : 0.0));
+    double Rn = R;
+    for (int k = 2; k < N; ++k) {
+        Rn *= R;
+        J[k] = (Z * Rn + k * q2 * J[k - 2]) / (k + 1.0);
+    }
+    double s = 0.0;
+    for (int k = 0; k < N; ++k) s += c[k] * J[k];
+    return s;
+}
+// F(q) = 2 int_0^sqrt(4 - q^2) w(sqrt(q^2 + z^2)) dz for 0 <= q < 2.
+__device__ double column_F(int kid, double q) {
+    const double Zm = sqrt(fmax(4.0 - q * q, 0.0));
+    if (kid == ASP_KERNEL_WENDLAND_C2_COLUMN) {  // (1 - r/2)^4 (1 + 2r) by powers of r
+        const double c[6] = {1.0, 0.0, -2.5, 2.5, -15.0 / 16.0, 0.125};
+        return 2.0 * column_piece(c, q, Zm);
+    }
+    const double out[4] = {2.0, -3.0, 1.5, -0.25};  // (2 - r)^3 / 4
+    double F = column_piece(out, q, Zm);
+    if (q < 1.0) {  // the inner polynomial replaces the outer one on [0, sqrt(1 - q^2)]
+        const double in[4] = {1.0, 0.0, -1.5, 0.75};
+        const double Z1 = sqrt(1.0 - q * q);
+        F += column_piece(in, q, Z1) - column_piece(out, q, Z1);
+    }
+    return 2.0 * F;
+}
+
 __global__ void k_kernel_eval(int kid, const double* __restrict__ r, const double* __restrict__ h,
                               double* __restrict__ w, long long n) {
     long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     double q = r[i] / h[i];
     double res = 0.0;
-    if (kid == ASP_KERNEL_CUBIC_SPLINE) {  // _kernels.pyx:13-19, same branch order
+    if (kid == ASP_KERNEL_CUBIC_SPLINE_COLUMN || kid == ASP_KERNEL_WENDLAND_C2_COLUMN) {
+        // as ids 0 and 1: inside the support or exactly 0 (h == 0 makes q infinite or NaN:
+        // 0).  The integral is even in q, so a negative h is evaluated at |q|.
+        const double K = kid == ASP_KERNEL_CUBIC_SPLINE_COLUMN ? 1.0 / M_PI : 21.0 / (16.0 * M_PI);
+        if (fabs(q) < 2.0) res = K * column_F(kid, fabs(q)) / (h[i] * h[i]);
+    } else if (kid == ASP_KERNEL_CUBIC_SPLINE) {  // _kernels.pyx:13-19, same branch order
         if (q < 1.0)
             res = (1 - 1.5 * pow(q, 2.0) + 0.75 * pow(q, 3.0)) / (M_PI * pow(h[i], 3.0));
         else if (q < 2.0)
@@ -114,7 +156,8 @@ int asp_kernel_eval(int32_t kernel_id, const double* r, const double* h, double*
                     int32_t flags, int32_t device, void* stream) {
     enum { kR, kH, kW };  // per-call scratch of a host caller: staged r, h and the values
     t_err.clear();
-    if (kernel_id < 0 || kernel_id > 2) return fail(ASP_ERR_INVALID, "unknown kernel_id");
+    if (kernel_id < 0 || kernel_id > ASP_KERNEL_WENDLAND_C2_COLUMN)
+        return fail(ASP_ERR_INVALID, "unknown kernel_id");
     if (n < 0) return fail(ASP_ERR_INVALID, "n < 0");
     if (n == 0) return ASP_OK;
     return with_workspace(device, (hipStream_t)stream, false, [&](Workspace& ws, hipStream_t st) -> int {

@@ -502,7 +502,8 @@ struct Props {
 static int check_args(const void* a1, const float* out0, const float* out1, long long n, int kid,
                       int flags) {
     if (n < 0) return fail(ASP_ERR_INVALID, "n < 0");
-    if (kid < 0 || kid > 2) return fail(ASP_ERR_INVALID, "unknown kernel_id");
+    if (kid < 0 || kid > ASP_KERNEL_WENDLAND_C2_COLUMN)
+        return fail(ASP_ERR_INVALID, "unknown kernel_id");
     if (!out0) return fail(ASP_ERR_INVALID, "out0 is NULL");
     if ((a1 == nullptr) != (out1 == nullptr))
         return fail(ASP_ERR_INVALID, "a1 and out1 must both be given or both be NULL");

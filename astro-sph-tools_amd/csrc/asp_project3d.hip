@@ -1098,6 +1098,9 @@ static int project3d(const float* x, const float* y, const float* z, const float
                      int k_lo, int k_hi, int kid, int flags, float* out, int device,
                      void* stream) {
     if (n < 0) return fail(ASP_ERR_INVALID, "n < 0");
+    if (kid == ASP_KERNEL_CUBIC_SPLINE_COLUMN || kid == ASP_KERNEL_WENDLAND_C2_COLUMN)
+        return fail(ASP_ERR_INVALID, "column-integrated kernels have no 3-D form: a cube takes "
+                                     "kernel ids 0 to 2");
     if (kid < 0 || kid > 2) return fail(ASP_ERR_INVALID, "unknown kernel_id");
     if (!out) return fail(ASP_ERR_INVALID, "out is NULL");
     if (flags & ~(ASP_F_DEVICE_PTRS | ASP_F_ACCUMULATE))

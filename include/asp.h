@@ -34,11 +34,20 @@ extern "C" {
 
 #define ASP_API_VERSION 1
 
-/* kernel_id: the SPH kernel W(r, h), support 2h, 3-D normalisation, evaluated at the
- * projected 2-D distance (reference semantics S6). */
+/* kernel_id: the SPH kernel W(r, h), support 2h, evaluated at the projected 2-D distance
+ * r of a (particle, pixel corner) pair.  Ids 0 and 1 are the reference's semantics (S6):
+ * the 3-D-normalised kernel, ~ 1/h^3, so a map has units [A]/L^3.  Ids 3 and 4 are the
+ * same two kernels integrated along the line of sight,
+ *   W_col(r, h) = (K/h^2) F(q),  F(q) = 2 int_0^sqrt(4-q^2) w(sqrt(q^2 + z^2)) dz,  q = r/h,
+ * 2-D-normalised (2 pi int W_col r dr = 1): a map is a column density, [A]/L^2, and its
+ * sum times the pixel area is sum A.  The neighbour test r^2 < (2h)^2, the chunk cull and
+ * every entry point's arguments are the same for all ids; the column kernels have no 3-D
+ * form (asp_project3d returns ASP_ERR_INVALID for them). */
 #define ASP_KERNEL_CUBIC_SPLINE 0 /* _kernels.pyx:9-20 quartic_spline_kernel (M4 cubic)  */
 #define ASP_KERNEL_WENDLAND_C2 1  /* 21/(16 pi h^3) (1-q/2)^4 (1+2q), build-defined      */
 #define ASP_KERNEL_INDICATOR 2    /* W = 1 for every included pair: neighbour counting    */
+#define ASP_KERNEL_CUBIC_SPLINE_COLUMN 3 /* column integral of id 0: 3/(2 pi h^2) at q = 0 */
+#define ASP_KERNEL_WENDLAND_C2_COLUMN 4  /* column integral of id 1: 7/(4 pi h^2) at q = 0 */
 
 /* flags */
 #define ASP_F_DEVICE_PTRS 0x1 /* inputs/outputs are device pointers on `device`            */
