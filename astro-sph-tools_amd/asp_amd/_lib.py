@@ -47,7 +47,7 @@ EXPORTS = ("asp_version", "asp_last_error", "asp_device_count", "asp_project2d",
            "asp_profile", "asp_profile_stages", "asp_profile_read", "asp_last_stats",
            "asp_release", "asp_stage_particles", "asp_periodic", "asp_wrapped_distance",
            "asp_knn_smoothing_lengths", "asp_table_interp3", "asp_table_interp", "asp_nearest",
-           "asp_match_ids", "asp_take_rows")
+           "asp_match_ids", "asp_take_rows", "asp_sample2d", "asp_sample2d_f64")
 
 ASP_MATCH_MAPPING = 0
 ASP_MATCH_REORDER = 1
@@ -56,6 +56,9 @@ STAGES = ("memset", "count", "colscan", "tilescan", "scatter", "scale", "deposit
           "wide", "ratio", "cube_count", "cube_colscan", "cube_tilescan", "cube_scatter",
           "cube_deposit", "cube_merge", "gather", "knn_prep", "knn_search", "nearest_prep",
           "nearest_search")
+# asp_sample2d's stages, numbered after STAGES (21, 22)
+SAMPLE_STAGES = ("sample_prep", "sample_deposit")
+ALL_STAGES = STAGES + SAMPLE_STAGES
 
 _lib = None
 
@@ -167,6 +170,12 @@ def lib():
                                 _i64, C.c_int32, C.c_int32, C.c_void_p]
     L.asp_take_rows.argtypes = [C.c_void_p, C.c_int64, C.c_int64, _i32, C.c_int64, C.c_void_p,
                                 C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    if hasattr(L, "asp_sample2d"):  # (absent from an older A/B build, ASP_LIB)
+        L.asp_sample2d.argtypes = [_f, _f, _f, _f, _f, C.c_int64, _d, _d, C.c_int64, C.c_int32,
+                                   C.c_int32, _f, _f, C.c_int32, C.c_void_p]
+        L.asp_sample2d_f64.argtypes = [_d, _d, _d, _d, C.c_int64, C.c_int32, _d, _d, C.c_int64,
+                                       C.c_int32, C.c_int32, _f, _f, C.c_int32, C.c_void_p]
+        L.asp_sample2d.restype = L.asp_sample2d_f64.restype = C.c_int
     for name in ("asp_match_ids", "asp_take_rows", "asp_nearest", "asp_project2d", "asp_project2d_f64", "asp_pairs_begin", "asp_pairs_emit",
                  "asp_pairs_end", "asp_project3d", "asp_kernel_eval", "asp_chunk_ranges",
                  "asp_pixel_neighbours", "asp_ratio", "asp_profile", "asp_profile_stages",
@@ -220,19 +229,19 @@ def last_stats(device: int = 0):
 
 def profile(device: int = 0, enable: bool = True, stages=None):
     """Start (and reset) / stop per-stage HIP-event timing inside the library; ``stages``
-    (names of STAGES) limits the events to those stages."""
+    (names of ALL_STAGES) limits the events to those stages."""
     if stages is None or not enable:
         check(lib().asp_profile(device, 1 if enable else 0))
     else:
         mask = 0
         for s in stages:
-            mask |= 1 << STAGES.index(s)
+            mask |= 1 << ALL_STAGES.index(s)
         check(lib().asp_profile_stages(device, mask))
 
 
 def profile_read(device: int = 0):
     """{stage: (total_ms, launches)} since the last reset."""
-    ms = (C.c_double * len(STAGES))()
-    n = (C.c_int64 * len(STAGES))()
-    check(lib().asp_profile_read(device, ms, n, len(STAGES)))
-    return {s: (ms[i], n[i]) for i, s in enumerate(STAGES)}
+    ms = (C.c_double * len(ALL_STAGES))()
+    n = (C.c_int64 * len(ALL_STAGES))()
+    check(lib().asp_profile_read(device, ms, n, len(ALL_STAGES)))
+    return {s: (ms[i], n[i]) for i, s in enumerate(ALL_STAGES)}

@@ -73,7 +73,7 @@ struct Buf {
     size_t cap = 0;
 };
 
-constexpr int kStages = 21;
+constexpr int kStages = 23;
 constexpr int kNStats = 15;  // asp_last_stats
 constexpr int kMarks = 8;  // launches of one stage timed per call
 enum Stage {
@@ -84,11 +84,13 @@ enum Stage {
     kSGather = 16,  // 2-D gathered deposit of the large-record stream
     kSKnnPrep = 17, kSKnnSearch = 18,  // k-NN: keys / sort / tables; the search kernel
     // asp_nearest: centre check / cell sort; the search (with the query sort, when on)
-    kSNearestPrep = 19, kSNearestSearch = 20
+    kSNearestPrep = 19, kSNearestSearch = 20,
+    // asp_sample2d: point keys / sort / cell offsets; the particle -> point deposit
+    kSSamplePrep = 21, kSSampleDeposit = 22
 };
 
 // What the slots of the workspace's buffer arrays hold (Workspace::knn, nearest, match,
-// aux, pairs).
+// sample, aux, pairs).
 // asp_knn_smoothing_lengths
 enum KnnBuf {
     kKnnPos, kKnnH,            // staged positions and smoothing lengths (host callers)
@@ -126,6 +128,20 @@ enum MatchBuf {
     kMatchRows, kMatchRowsOut, kMatchRowIndex,  // asp_take_rows: staged rows, output, index
     kMatchBufCount
 };
+// asp_sample2d / asp_sample2d_f64
+enum SampleBuf {
+    kSmpPart0, kSmpPart1, kSmpPart2, kSmpPart3, kSmpPart4,  // staged particle arrays (host callers)
+    kSmpPx, kSmpPy,            // staged point coordinates
+    kSmpOut0, kSmpOut1,        // staged outputs
+    kSmpDesc,                  // the point grid's descriptor (bounding box, scales, counters)
+    kSmpKeys, kSmpIndex,       // cell keys and point indices, in / out
+    kSmpSortTmp,               // radix sort scratch
+    kSmpCellCount, kSmpCellStart,  // points per cell and their exclusive scan
+    kSmpScanTmp,               // scan scratch
+    kSmpSorted,                // point coordinates in cell order (x, then y)
+    kSmpAcc,                   // per-point accumulators (fp64 or int64), in cell order
+    kSampleBufCount
+};
 // Per-call scratch that several entry points reuse, each with its own meaning for slots
 // 0 .. 4 (a local enum at the top of the user); the last holds a call's few 64-bit
 // counter words (asp_stage_particles' image counts, the ASP_COUNT_EVALS sums).
@@ -139,6 +155,7 @@ struct WorkspaceBufs {
     Buf knn[kKnnBufCount];
     Buf nearest[kNearestBufCount];
     Buf match[kMatchBufCount];
+    Buf sample[kSampleBufCount];
     Buf aux[kAuxBufCount];
     Buf in[5], out[2], hist, cmx, tile_total, tile_start, tile_k, items, merges, counters, recs,
         wide, slabs, morton, iorder;

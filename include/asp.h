@@ -393,6 +393,73 @@ int asp_nearest(const double *positions, int64_t n, const double *centres, int64
                 double *distance, int32_t flags, int32_t device, void *stream);
 
 /*
+ * SPH sums at arbitrary points -- sightline columns: calculate_pixel_value
+ * (_pixel_calculations.pyx:9-36), the reference's point-wise unit of work, at M arbitrary
+ * positions instead of the corners of a pixel grid (the positions and directions of
+ * LineOfSightFileBase, _LineOfSightBase.py:16-73, for sightlines along the projection axis).
+ * With kernel ids 3 / 4 and ion masses from asp_table_interp the result is the column density
+ * at the sightline itself.
+ *
+ *   out0[k] = sum_p a0[p] * W(r, h_p)  over p with  r2 = dx*dx + dy*dy < (2 h_p)*(2 h_p),
+ *   dx = u_p - px[k],  dy = v_p - py[k]
+ *
+ * -- every quantity of the test in fp64, in the reference's operation order (.pyx:20-31), no
+ * fused multiply-add; there is NO chunk cull (that is create_image's).  Neighbour sets are
+ * bit-exact: asp_sample2d decides on the fp64 values of its fp32 inputs, asp_sample2d_f64 on
+ * the reader's fp64 arrays themselves (positions (n, 3) row-major, axis 0 / 1 / 2 selecting
+ * the columns as asp_project2d_f64 does; an axis carrying ASP_AXIS_CULL bits is
+ * ASP_ERR_INVALID: there is no cull to redirect).  Values: fp32 terms from the map's own
+ * term arithmetic (the fp64 entry rounds h and a to fp32 once, as the map's staging does),
+ * the pair difference formed in fp64, accumulated in fp64 per point; kernel ids 0 .. 4.
+ * a1 / out1 (both NULL or both non-NULL) give a second sum over the same neighbour sets.
+ * px, py: fp64 point coordinates in the projected (u, v) frame; out0 / out1: m floats.
+ *
+ * flags: ASP_F_DEVICE_PTRS (every pointer, px / py included, is a device pointer; the work
+ * is ordered on `stream`), ASP_F_RATIO (out0 <- out0 / out1, 0 where out1 == 0; needs out1,
+ * not with ASP_F_ACCUMULATE), ASP_F_ACCUMULATE (add into the outputs), ASP_F_DETERMINISTIC
+ * (int64 fixed point on ONE scale per output, a power of two taken from n and
+ * max_p |a_p| W(0, h_p): bitwise reproducible, independent of the order of the particles and
+ * of the points; each term is rounded to <= 2^-46 max|a W(0)|, 2^-57 n max|a W(0)| when that
+ * is larger; not with ASP_F_RATIO).  ASP_F_DEVICE_OUTPUTS: ASP_ERR_INVALID.
+ *
+ * Sizes: n == 0 gives zeros (the outputs untouched under ASP_F_ACCUMULATE); m == 0 is valid
+ * and needs no device; m >= 2^31 is ASP_ERR_UNSUPPORTED; any n runs in one call (batched
+ * internally, ASP_MAX_BATCH).  n < 0, m < 0, NULL arrays with non-zero sizes, an unknown
+ * kernel id, one of a1 / out1 without the other: ASP_ERR_INVALID before any device work,
+ * asp_last_error naming the condition.
+ *
+ * Odd values.  A point with a non-finite coordinate gets 0 (the reference's result: every
+ * comparison is false).  Particles are admitted as asp_project2d's footprint() admits them,
+ * on the fp32 working values: 2|h| must be > 0 and finite in fp32 and u, v finite in fp32 --
+ * h == 0, a non-finite h, u or v, or an h so large that 2h overflows fp32 contribute to no
+ * point.  A negative h passes the reference's test ((2h)^2 > 0), so the particle is in the
+ * neighbour set of the points inside its disc, as it is in the map's where the chunk cull
+ * lets it through; its term is the scalar form a K / h^3 f(r / h) with q = r / h < 0 -- not a
+ * physical value, and one the map's deposit paths do not form alike either.  A non-finite a of an admitted particle makes
+ * exactly the points inside its disc NaN (the map's NaN pixels contain those: its
+ * edge-continuous forms also reach the rest of the particle's candidate box); under
+ * ASP_F_DETERMINISTIC those points are unspecified.
+ *
+ * Method: the points are sorted into a uniform cell grid over their bounding
+ * box; each particle visits the cells its box meets -- a lane per particle, or the whole wave
+ * when the box meets more than ASP_SAMPLE_WIDE_CELLS cells (default 16) or those cells hold
+ * more than ASP_SAMPLE_WIDE_POINTS points (default 256: many sightlines on one position).  Workspace: 48 bytes
+ * per point plus 8 bytes per cell.  Periodic boxes: stage with asp_stage_particles(...,
+ * ASP_PB_IMAGES) and pass its fp32 device arrays here.  Environment (read per call; results
+ * have identical neighbour sets and stay within the value bar for every setting):
+ * ASP_SAMPLE_CELLS (cells per axis, 1 .. 2048; default ceil(sqrt(m / 4)) capped at 2048),
+ * ASP_SAMPLE_WIDE_CELLS, ASP_SAMPLE_WIDE_POINTS, ASP_SAMPLE_COUNT (diagnostic: asp_last_stats[9] = (particle, point)
+ * pairs tested; the map counters are 0 after a sample call).
+ */
+int asp_sample2d(const float *u, const float *v, const float *h, const float *a0, const float *a1,
+                 int64_t n, const double *px, const double *py, int64_t m, int32_t kernel_id,
+                 int32_t flags, float *out0, float *out1, int32_t device, void *stream);
+int asp_sample2d_f64(const double *positions, const double *h, const double *a0, const double *a1,
+                     int64_t n, int32_t axis, const double *px, const double *py, int64_t m,
+                     int32_t kernel_id, int32_t flags, float *out0, float *out1,
+                     int32_t device, void *stream);
+
+/*
  * Cross-snapshot ID matching: the numerical core of tools/_ArrayReorder.py -- ArrayReorder
  * (:815-1038) and ArrayMapping (:1042-1171), which line two ID orderings up with argsort /
  * isin / searchsorted over int64 IDs (:1003-1038, :1057-1081).  For source IDs S with the
@@ -502,7 +569,8 @@ int asp_table_interp(const double *table, int32_t ndim, const int32_t *shape,
  * the passes), stats[14] scatter runs of the placement trials.  Images of more than 4096
  * tiles and batched calls: the sums over all passes.  After asp_knn_smoothing_lengths
  * (ASP_KNN_COUNT) and asp_nearest (ASP_NEAREST_COUNT) the words describe that call: stats[9]
- * = distances evaluated (asp_nearest: over all queries and sets), the map counters 0.
+ * = distances evaluated (asp_nearest: over all queries and sets), the map counters 0; after
+ * asp_sample2d(_f64) with ASP_SAMPLE_COUNT stats[9] = (particle, point) pairs tested.
  */
 int asp_last_stats(int32_t device, int64_t *stats, int32_t nstats);
 
@@ -514,7 +582,9 @@ int asp_last_stats(int32_t device, int64_t *stats, int32_t nstats);
  * 8 wide, 9 ratio; cube (asp_project3d): 10 count, 11 colscan, 12 tilescan, 13 scatter,
  * 14 deposit, 15 merge; 16 gather (2-D gathered deposit of the large-record stream);
  * 17 knn_prep, 18 knn_search (asp_knn_smoothing_lengths); 19 nearest_prep, 20 nearest_search
- * (asp_nearest: the centre check and cell sort; the search, with the query sort when on).
+ * (asp_nearest: the centre check and cell sort; the search, with the query sort when on);
+ * 21 sample_prep, 22 sample_deposit (asp_sample2d: point keys, sort and cell offsets; the
+ * particle -> point deposit with the fixed-point scale and the finalising pass).
  */
 int asp_profile(int32_t device, int32_t enable);
 /* As asp_profile(device, 1), but events only around the stages whose bit is set in
