@@ -48,6 +48,16 @@ def axis_index(projection_axis) -> int:
     return i if i in (0, 1) else 2
 
 
+def axis_code(projection_axis) -> int:
+    """The C-ABI's ``axis`` argument: :func:`axis_index` of any spelling, or, for a
+    ``(pixel axis, cull axis)`` tuple (:func:`reference_axes`), the pixel axis with the cull
+    axis + 1 in bits 4-5 when the two differ (ASP_AXIS_CULL of include/asp.h)."""
+    if not isinstance(projection_axis, tuple):
+        return axis_index(projection_axis)
+    pixel, cull = int(projection_axis[0]), int(projection_axis[1])
+    return pixel if cull == pixel else pixel | (cull + 1) << 4
+
+
 def reference_axes(projection_axis):
     """(pixel axis, cull axis) exactly as the reference derives them from ANY value.
 

@@ -38,17 +38,6 @@ ASP_ERR_HIP = -2
 ASP_ERR_NOMEM = -3
 ASP_ERR_UNSUPPORTED = -4
 
-# Every symbol include/asp.h declares (tests check the library exports all of them).
-EXPORTS = ("asp_version", "asp_last_error", "asp_device_count", "asp_project2d",
-           "asp_project2d_rows", "asp_project2d_props", "asp_project2d_props_f64",
-           "asp_project2d_sph", "asp_project2d_sph_f64",
-           "asp_project2d_f64", "asp_pairs_begin", "asp_pairs_emit", "asp_pairs_end",
-           "asp_project3d", "asp_kernel_eval", "asp_chunk_ranges", "asp_pixel_neighbours", "asp_ratio",
-           "asp_profile", "asp_profile_stages", "asp_profile_read", "asp_last_stats",
-           "asp_release", "asp_stage_particles", "asp_periodic", "asp_wrapped_distance",
-           "asp_knn_smoothing_lengths", "asp_table_interp3", "asp_table_interp", "asp_nearest",
-           "asp_match_ids", "asp_take_rows", "asp_sample2d", "asp_sample2d_f64")
-
 ASP_MATCH_MAPPING = 0
 ASP_MATCH_REORDER = 1
 
@@ -67,6 +56,56 @@ _d = C.POINTER(C.c_double)
 _i32 = C.POINTER(C.c_int32)
 _i64 = C.POINTER(C.c_int64)
 _u8 = C.POINTER(C.c_uint8)
+
+# The C-ABI of include/asp.h, one entry per function: its argument types.  lib() applies them;
+# a new entry point adds its line here and nothing else in this module.
+_I, _Q, _R, _V = C.c_int32, C.c_int64, C.c_double, C.c_void_p
+_GRID2 = [_R] * 4 + [_I] * 3  # x_min, x_max, y_min, y_max, nx, ny, chunk_size
+PROTOTYPES = {
+    "asp_version": [],
+    "asp_last_error": [],
+    "asp_device_count": [],
+    "asp_project2d": [_f] * 5 + [_Q] + _GRID2 + [_I, _I, _f, _f, _I, _V],
+    "asp_project2d_rows": [_f] * 5 + [_Q] + _GRID2 + [_I] * 4 + [_f, _f, _I, _V],
+    "asp_project2d_props": [_f, _f, _f, C.POINTER(_f), _I, _Q] + _GRID2
+                           + [_I, _I, C.POINTER(_f), _I, _V],
+    "asp_project2d_props_f64": [_d, _d, C.POINTER(_d), _I, _Q, _I] + _GRID2
+                               + [_I, _I, C.POINTER(_f), _I, _V],
+    "asp_project2d_sph": [_f] * 5 + [C.POINTER(_f), _I, _Q] + _GRID2
+                         + [_I, _I, C.POINTER(_f), _I, _V],
+    "asp_project2d_sph_f64": [_d] * 4 + [C.POINTER(_d), _I, _Q, _I] + _GRID2
+                             + [_I, _I, C.POINTER(_f), _I, _V],
+    "asp_project2d_f64": [_d] * 4 + [_Q, _I] + _GRID2 + [_I, _I, _f, _f, _I, _V],
+    "asp_pairs_begin": [_d, _d, _Q, _I] + _GRID2 + [_I, _I, _V, _i64, C.POINTER(_V)],
+    "asp_pairs_emit": [_V, _I, _I, _i64, _i32, _d],
+    "asp_pairs_end": [_V],
+    "asp_project3d": [_f] * 5 + [_Q] + [_R] * 6 + [_I] * 7 + [_f, _I, _V],
+    "asp_kernel_eval": [_I, _d, _d, _d, _Q, _I, _I, _V],
+    "asp_chunk_ranges": [_f, _f, _f, _Q] + _GRID2 + [_i32] * 4 + [_I, _I, _V],
+    "asp_pixel_neighbours": [_f, _f, _f, _Q] + _GRID2 + [_i64, _Q, _i64, _i32, _Q, _i64, _I],
+    "asp_ratio": [_f, _f, _Q, _I, _V],
+    "asp_profile": [_I, _I],
+    "asp_profile_stages": [_I, C.c_uint32],
+    "asp_profile_read": [_I, _d, _i64, _I],
+    "asp_last_stats": [_I, _i64, _I],
+    "asp_release": [_I],
+    "asp_stage_particles": [_d] * 4 + [_Q, _I, _d, _R, _I] + [_f] * 5 + [_Q, _i64, _I, _I, _V],
+    "asp_periodic": [_I, _d, _Q, _d, _Q, _Q, _R, _I, _d, _I, _V],
+    "asp_wrapped_distance": [_d, _Q, _d, _Q, _Q, _R, _I, _d, _I, _V],
+    "asp_knn_smoothing_lengths": [_d, _Q, _I, _d, _I, _I, _V],
+    "asp_table_interp3": [_d, _I, _I, _I, _d, _d, _d, _d, _I, _I, _R, _Q, _R, _I, _d, _d, _d,
+                          _I, _V],
+    "asp_table_interp": [_d, _I, _i32, C.POINTER(_V), _d, _I, _I, _R, _Q, _R, _I, _I, _d, _d,
+                         _d, _I, _V],
+    "asp_nearest": [_d, _Q, _d, _Q, C.POINTER(C.c_uint32), _I, _R, _i32, _d, _I, _I, _V],
+    "asp_match_ids": [_i64, _u8, _Q, _i64, _u8, _Q, _I, _i32, _u8, _i64, _I, _I, _V],
+    "asp_take_rows": [_V, _Q, _Q, _i32, _Q, _V, _V, _I, _I, _V],
+    "asp_sample2d": [_f] * 5 + [_Q, _d, _d, _Q, _I, _I, _f, _f, _I, _V],
+    "asp_sample2d_f64": [_d] * 4 + [_Q, _I, _d, _d, _Q, _I, _I, _f, _f, _I, _V],
+}
+RESTYPES = {"asp_last_error": C.c_char_p}  # every other function returns int
+# Every symbol include/asp.h declares (tests check the library exports all of them).
+EXPORTS = tuple(PROTOTYPES)
 
 
 class ASPError(RuntimeError):
@@ -93,96 +132,10 @@ def lib():
         except Exception:
             pass
     L = C.CDLL(LIB_PATH)
-    L.asp_version.restype = C.c_int
-    L.asp_last_error.restype = C.c_char_p
-    L.asp_device_count.restype = C.c_int
-    L.asp_project2d.argtypes = [_f, _f, _f, _f, _f, C.c_int64, C.c_double, C.c_double,
-                                C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32,
-                                C.c_int32, C.c_int32, _f, _f, C.c_int32, C.c_void_p]
-    if hasattr(L, "asp_project2d_rows"):  # (absent from an older A/B build, ASP_LIB)
-      L.asp_project2d_rows.argtypes = [_f, _f, _f, _f, _f, C.c_int64, C.c_double, C.c_double,
-                                       C.c_double, C.c_double, C.c_int32, C.c_int32,
-                                       C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                       _f, _f, C.c_int32, C.c_void_p]
-    if hasattr(L, "asp_project2d_props"):  # (absent from an older A/B build, ASP_LIB)
-        L.asp_project2d_props.argtypes = [_f, _f, _f, C.POINTER(_f), C.c_int32, C.c_int64,
-                                          C.c_double, C.c_double, C.c_double, C.c_double,
-                                          C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                          C.POINTER(_f), C.c_int32, C.c_void_p]
-        L.asp_project2d_props_f64.argtypes = [_d, _d, C.POINTER(_d), C.c_int32, C.c_int64,
-                                              C.c_int32, C.c_double, C.c_double, C.c_double,
-                                              C.c_double, C.c_int32, C.c_int32, C.c_int32,
-                                              C.c_int32, C.c_int32, C.POINTER(_f), C.c_int32,
-                                              C.c_void_p]
-    if hasattr(L, "asp_project2d_sph"):
-        L.asp_project2d_sph.argtypes = [_f, _f, _f, _f, _f, C.POINTER(_f), C.c_int32, C.c_int64,
-                                        C.c_double, C.c_double, C.c_double, C.c_double,
-                                        C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                        C.POINTER(_f), C.c_int32, C.c_void_p]
-        L.asp_project2d_sph_f64.argtypes = [_d, _d, _d, _d, C.POINTER(_d), C.c_int32, C.c_int64,
-                                            C.c_int32, C.c_double, C.c_double, C.c_double,
-                                            C.c_double, C.c_int32, C.c_int32, C.c_int32,
-                                            C.c_int32, C.c_int32, C.POINTER(_f), C.c_int32,
-                                            C.c_void_p]
-    L.asp_project2d_f64.argtypes = [_d, _d, _d, _d, C.c_int64, C.c_int32, C.c_double,
-                                    C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32,
-                                    C.c_int32, C.c_int32, C.c_int32, _f, _f, C.c_int32,
-                                    C.c_void_p]
-    L.asp_pairs_begin.argtypes = [_d, _d, C.c_int64, C.c_int32, C.c_double, C.c_double,
-                                  C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32,
-                                  C.c_int32, C.c_int32, C.c_void_p, _i64, C.POINTER(C.c_void_p)]
-    L.asp_pairs_emit.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _i64, _i32, _d]
-    L.asp_pairs_end.argtypes = [C.c_void_p]
-    L.asp_project3d.argtypes = ([_f] * 5 + [C.c_int64] + [C.c_double] * 6 + [C.c_int32] * 7
-                                + [_f, C.c_int32, C.c_void_p])
-    L.asp_kernel_eval.argtypes = [C.c_int32, _d, _d, _d, C.c_int64, C.c_int32, C.c_int32,
-                                  C.c_void_p]
-    L.asp_chunk_ranges.argtypes = [_f, _f, _f, C.c_int64, C.c_double, C.c_double, C.c_double,
-                                   C.c_double, C.c_int32, C.c_int32, C.c_int32, _i32, _i32,
-                                   _i32, _i32, C.c_int32, C.c_int32, C.c_void_p]
-    L.asp_pixel_neighbours.argtypes = [_f, _f, _f, C.c_int64, C.c_double, C.c_double,
-                                       C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32,
-                                       _i64, C.c_int64, _i64, _i32, C.c_int64, _i64, C.c_int32]
-    L.asp_ratio.argtypes = [_f, _f, C.c_int64, C.c_int32, C.c_void_p]
-    L.asp_profile.argtypes = [C.c_int32, C.c_int32]
-    L.asp_profile_stages.argtypes = [C.c_int32, C.c_uint32]
-    L.asp_profile_read.argtypes = [C.c_int32, _d, _i64, C.c_int32]
-    L.asp_last_stats.argtypes = [C.c_int32, _i64, C.c_int32]
-    L.asp_release.argtypes = [C.c_int32]
-    L.asp_stage_particles.argtypes = [_d, _d, _d, _d, C.c_int64, C.c_int32, _d, C.c_double,
-                                      C.c_int32, _f, _f, _f, _f, _f, C.c_int64, _i64, C.c_int32,
-                                      C.c_int32, C.c_void_p]
-    L.asp_periodic.argtypes = [C.c_int32, _d, C.c_int64, _d, C.c_int64, C.c_int64, C.c_double,
-                               C.c_int32, _d, C.c_int32, C.c_void_p]
-    L.asp_wrapped_distance.argtypes = [_d, C.c_int64, _d, C.c_int64, C.c_int64, C.c_double,
-                                       C.c_int32, _d, C.c_int32, C.c_void_p]
-    L.asp_knn_smoothing_lengths.argtypes = [_d, C.c_int64, C.c_int32, _d, C.c_int32, C.c_int32,
-                                            C.c_void_p]
-    L.asp_table_interp3.argtypes = ([_d, C.c_int32, C.c_int32, C.c_int32, _d, _d, _d, _d,
-                                     C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_double,
-                                     C.c_int32, _d, _d, _d, C.c_int32, C.c_void_p])
-    L.asp_table_interp.argtypes = ([_d, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_void_p),
-                                    _d, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_double,
-                                    C.c_int32, C.c_int32, _d, _d, _d, C.c_int32, C.c_void_p])
-    L.asp_nearest.argtypes = [_d, C.c_int64, _d, C.c_int64, C.POINTER(C.c_uint32), C.c_int32,
-                              C.c_double, _i32, _d, C.c_int32, C.c_int32, C.c_void_p]
-    L.asp_match_ids.argtypes = [_i64, _u8, C.c_int64, _i64, _u8, C.c_int64, C.c_int32, _i32, _u8,
-                                _i64, C.c_int32, C.c_int32, C.c_void_p]
-    L.asp_take_rows.argtypes = [C.c_void_p, C.c_int64, C.c_int64, _i32, C.c_int64, C.c_void_p,
-                                C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
-    if hasattr(L, "asp_sample2d"):  # (absent from an older A/B build, ASP_LIB)
-        L.asp_sample2d.argtypes = [_f, _f, _f, _f, _f, C.c_int64, _d, _d, C.c_int64, C.c_int32,
-                                   C.c_int32, _f, _f, C.c_int32, C.c_void_p]
-        L.asp_sample2d_f64.argtypes = [_d, _d, _d, _d, C.c_int64, C.c_int32, _d, _d, C.c_int64,
-                                       C.c_int32, C.c_int32, _f, _f, C.c_int32, C.c_void_p]
-        L.asp_sample2d.restype = L.asp_sample2d_f64.restype = C.c_int
-    for name in ("asp_match_ids", "asp_take_rows", "asp_nearest", "asp_project2d", "asp_project2d_f64", "asp_pairs_begin", "asp_pairs_emit",
-                 "asp_pairs_end", "asp_project3d", "asp_kernel_eval", "asp_chunk_ranges",
-                 "asp_pixel_neighbours", "asp_ratio", "asp_profile", "asp_profile_stages",
-                 "asp_profile_read", "asp_last_stats", "asp_release", "asp_stage_particles",
-                 "asp_periodic", "asp_wrapped_distance", "asp_knn_smoothing_lengths",
-                 "asp_table_interp3", "asp_table_interp"):
-        getattr(L, name).restype = C.c_int
+    for name, argtypes in PROTOTYPES.items():
+        fn = getattr(L, name, None)  # (absent from an older A/B build, ASP_LIB)
+        if fn is not None:
+            fn.argtypes, fn.restype = argtypes, RESTYPES.get(name, C.c_int)
     _lib = L
     return L
 

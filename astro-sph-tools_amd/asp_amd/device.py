@@ -6,21 +6,10 @@ only provides the device memory and the stream; all compute is libasp_hip.so.
 from __future__ import annotations
 
 from . import _lib
-
-_KERNEL_NAMES = {"cubic": _lib.ASP_KERNEL_CUBIC_SPLINE, "quartic_spline_kernel": 0,
-                 "cubic_spline": 0, "wendland_c2": _lib.ASP_KERNEL_WENDLAND_C2,
-                 "indicator": _lib.ASP_KERNEL_INDICATOR,
-                 "cubic_column": _lib.ASP_KERNEL_CUBIC_SPLINE_COLUMN,
-                 "wendland_c2_column": _lib.ASP_KERNEL_WENDLAND_C2_COLUMN}
-
-
-def kernel_id(kernel) -> int:
-    if isinstance(kernel, int):
-        return kernel
-    if isinstance(kernel, str):
-        return _KERNEL_NAMES[kernel]
-    from .tools.projections._kernels import native_kernel_id
-    return native_kernel_id(kernel)
+from ._axes import axis_code
+from ._call import (alloc_out, call_flags, dev_f64, dptr, host_f64, is_device, positions_f64,
+                    raw_stream, stream_scope, upload_f64)
+from .tools.projections._kernels import device_kernel_id as kernel_id  # noqa: F401
 
 
 def _check(t, name, n=None, device=None):
@@ -56,24 +45,12 @@ def project2d(u, v, h, a0, a1=None, *, image_size, extent, chunk_size: int = 64,
     r0, r1 = (0, nx) if rows is None else (int(rows[0]), int(rows[1]))
     if not 0 <= r0 < r1 <= nx:
         raise ValueError(f"rows must satisfy 0 <= row_lo < row_hi <= nx, got {(r0, r1)}")
-    mx = r1 - r0  # rows written
-    if out0 is None:
-        out0 = torch.empty((mx, ny), dtype=torch.float32, device=dev)
-    if a1 is not None and out1 is None:
-        out1 = torch.empty((mx, ny), dtype=torch.float32, device=dev)
-    for t in (out0, out1):
-        if t is not None and (t.dtype != torch.float32 or t.device != dev or not t.is_contiguous()
-                              or t.numel() != mx * ny):
-            raise ValueError("outputs must be contiguous float32 (rows, ny) tensors on the device")
-    flags = _lib.ASP_F_DEVICE_PTRS
-    if ratio:
-        flags |= _lib.ASP_F_RATIO
-    if accumulate:
-        flags |= _lib.ASP_F_ACCUMULATE
-    if deterministic:
-        flags |= _lib.ASP_F_DETERMINISTIC
-    if stream is None:
-        stream = torch.cuda.current_stream(dev).cuda_stream
+    shape = (r1 - r0, ny)  # the rows written
+    out0 = alloc_out(shape, torch.float32, dev, out0)
+    if a1 is not None or out1 is not None:
+        out1 = alloc_out(shape, torch.float32, dev, out1)
+    flags = call_flags(True, ratio, accumulate, deterministic)
+    stream = raw_stream(stream, dev)
     P = _lib.ptr
     x_min, x_max, y_min, y_max = (float(e) for e in extent)
     if rows is None:
@@ -86,6 +63,15 @@ def project2d(u, v, h, a0, a1=None, *, image_size, extent, chunk_size: int = 64,
             int(chunk_size), r0, r1, kernel_id(kernel), flags, P(out0), P(out1), dev.index or 0,
             stream))
     return out0, (out1 if a1 is not None else None)
+
+
+def _check_props(k, mass, density, ratio):
+    if not 1 <= k <= 6:
+        raise ValueError("props: 1 .. 6 arrays")
+    if density is not None and mass is None:
+        raise ValueError("density needs mass (the weights are m / rho)")
+    if ratio and k != 2:
+        raise ValueError("ratio needs exactly two properties")
 
 
 def project2d_props(u, v, h, props, *, image_size, extent, chunk_size: int = 64,
@@ -102,42 +88,26 @@ def project2d_props(u, v, h, props, *, image_size, extent, chunk_size: int = 64,
     dev = u.device
     n = u.shape[0]
     k = len(props)
-    if not 1 <= k <= 6:
-        raise ValueError("props: 1 .. 6 arrays")
-    for t, name in ((u, "u"), (v, "v"), (h, "h")):
+    _check_props(k, mass, density, ratio)
+    for t, name in ((u, "u"), (v, "v"), (h, "h"), *((a, f"props[{j}]") for j, a in enumerate(props))):
         _check(t, name, n, dev)
-    for j, a in enumerate(props):
-        _check(a, f"props[{j}]", n, dev)
-    if density is not None and mass is None:
-        raise ValueError("density needs mass (the weights are m / rho)")
     for t, name in ((mass, "mass"), (density, "density")):
         if t is not None:
             _check(t, name, n, dev)
-    if ratio and k != 2:
-        raise ValueError("ratio needs exactly two properties")
     nx, ny = int(image_size[0]), int(image_size[1])
     if outs is None:
-        outs = [torch.empty((nx, ny), dtype=torch.float32, device=dev) for _ in range(k)]
+        outs = [None] * k
     if len(outs) != k:
         raise ValueError("one output per property")
-    for t in outs:
-        if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() or \
-                t.numel() != nx * ny:
-            raise ValueError("outputs must be contiguous float32 (nx, ny) tensors on the device")
-    flags = _lib.ASP_F_DEVICE_PTRS | (_lib.ASP_F_ACCUMULATE if accumulate else 0) | \
-        (_lib.ASP_F_RATIO if ratio else 0)
-    if stream is None:
-        stream = torch.cuda.current_stream(dev).cuda_stream
+    outs = [alloc_out((nx, ny), torch.float32, dev, o) for o in outs]
     P = _lib.ptr
     pa = (_lib._f * k)(*[P(a) for a in props])
     po = (_lib._f * k)(*[P(o) for o in outs])
     x_min, x_max, y_min, y_max = (float(e) for e in extent)
-    tail = (n, x_min, x_max, y_min, y_max, nx, ny, int(chunk_size), kernel_id(kernel), flags, po,
-            dev.index or 0, stream)
+    tail = (n, x_min, x_max, y_min, y_max, nx, ny, int(chunk_size), kernel_id(kernel),
+            call_flags(True, ratio, accumulate), po, dev.index or 0, raw_stream(stream, dev))
     if mass is not None:
-        _lib.check(_lib.lib().asp_project2d_sph(
-            P(u), P(v), P(h), P(mass), P(density) if density is not None else None, pa, k,
-            *tail))
+        _lib.check(_lib.lib().asp_project2d_sph(P(u), P(v), P(h), P(mass), P(density), pa, k, *tail))
     else:
         _lib.check(_lib.lib().asp_project2d_props(P(u), P(v), P(h), pa, k, *tail))
     return outs
@@ -151,77 +121,31 @@ def project2d_props_f64(positions, h, props, *, projection_axis=2, image_size, e
     one binning, every decision the reference's fp64 test.  Returns float32 device maps.
     ``mass`` / ``density`` / ``ratio``: as :func:`project2d_props` (asp_project2d_sph_f64;
     the weights m / rho are formed in fp64 from the reader's values)."""
-    import numpy as np
     import torch
-    from ._axes import axis_index
-    if isinstance(projection_axis, tuple):  # (pixel axis, cull axis): reference_axes()
-        axis = int(projection_axis[0])
-        if int(projection_axis[1]) != axis:
-            axis |= (int(projection_axis[1]) + 1) << 4  # ASP_AXIS_CULL
-    else:
-        axis = axis_index(projection_axis)
+    axis = axis_code(projection_axis)
     k = len(props)
-    if not 1 <= k <= 6:
-        raise ValueError("props: 1 .. 6 arrays")
-    dev = positions.device if hasattr(positions, "is_cuda") and positions.is_cuda \
-        else torch.device("cuda", device)
-
-    def on_dev(a, shape):
-        t = a if hasattr(a, "is_cuda") and a.is_cuda else torch.from_numpy(
-            np.ascontiguousarray(np.asarray(a), dtype=np.float64))
-        t = t.to(device=dev, dtype=torch.float64).contiguous()
-        if tuple(t.shape) != shape:
-            raise ValueError(f"array of shape {tuple(t.shape)}, expected {shape}")
-        return t
-
+    _check_props(k, mass, density, ratio)
+    dev = positions.device if is_device(positions) else torch.device("cuda", device)
     n = int(positions.shape[0])
-    pos = on_dev(positions, (n, 3))
-    hh = on_dev(np.asarray(h).reshape(-1) if not hasattr(h, "is_cuda") else h.reshape(-1), (n,))
-    pr = [on_dev(np.asarray(a).reshape(-1) if not hasattr(a, "is_cuda") else a.reshape(-1), (n,))
-          for a in props]
-    if density is not None and mass is None:
-        raise ValueError("density needs mass (the weights are m / rho)")
-    if ratio and k != 2:
-        raise ValueError("ratio needs exactly two properties")
-    flat = lambda a: np.asarray(a).reshape(-1) if not hasattr(a, "is_cuda") else a.reshape(-1)  # noqa: E731
-    wm = None if mass is None else on_dev(flat(mass), (n,))
-    wr = None if density is None else on_dev(flat(density), (n,))
-    nx, ny = int(image_size[0]), int(image_size[1])
-    outs = [torch.empty((nx, ny), dtype=torch.float32, device=dev) for _ in range(k)]
-    P = _lib.ptr
-    pa = (_lib._d * k)(*[P(a, _lib._d) for a in pr])
-    po = (_lib._f * k)(*[P(o) for o in outs])
-    x_min, x_max, y_min, y_max = (float(e) for e in extent)
-    flags = _lib.ASP_F_DEVICE_PTRS | (_lib.ASP_F_RATIO if ratio else 0)
-    tail = (n, axis, x_min, x_max, y_min, y_max, nx, ny, int(chunk_size), kernel_id(kernel), flags,
-            po, dev.index or 0, torch.cuda.current_stream(dev).cuda_stream)
-    if wm is not None:
-        _lib.check(_lib.lib().asp_project2d_sph_f64(
-            P(pos, _lib._d), P(hh, _lib._d), P(wm, _lib._d),
-            P(wr, _lib._d) if wr is not None else None, pa, k, *tail))
-    else:
-        _lib.check(_lib.lib().asp_project2d_props_f64(P(pos, _lib._d), P(hh, _lib._d), pa, k, *tail))
+    with stream_scope(dev, None) as scope:  # the uploads and casts ordered on the call's stream
+        pos = upload_f64(positions, "positions", (n, 3), dev, cast=True)[0]
+        hh, wm, wr, *pr = (None if a is None else upload_f64(a, name, (n,), dev, cast=True, flat=True)[0]
+                           for a, name in ((h, "h"), (mass, "mass"), (density, "density"),
+                                           *((a, f"props[{j}]") for j, a in enumerate(props))))
+        scope.keep(pos, hh, wm, wr, *pr)
+        nx, ny = int(image_size[0]), int(image_size[1])
+        outs = [alloc_out((nx, ny), torch.float32, dev) for _ in range(k)]
+        pa = (_lib._d * k)(*[dptr(a) for a in pr])
+        po = (_lib._f * k)(*[_lib.ptr(o) for o in outs])
+        x_min, x_max, y_min, y_max = (float(e) for e in extent)
+        tail = (n, axis, x_min, x_max, y_min, y_max, nx, ny, int(chunk_size), kernel_id(kernel),
+                call_flags(True, ratio), po, dev.index or 0, scope.raw)
+        if wm is not None:
+            _lib.check(_lib.lib().asp_project2d_sph_f64(dptr(pos), dptr(hh), dptr(wm), dptr(wr), pa,
+                                                        k, *tail))
+        else:
+            _lib.check(_lib.lib().asp_project2d_props_f64(dptr(pos), dptr(hh), pa, k, *tail))
     return outs
-
-
-def _f64_arg(a, name, n, shape_tail=()):
-    """A float64 input of create_image: a contiguous host array (NumPy / unyt) or a
-    float64 device tensor; returns (object keeping it alive, ctypes pointer, on_device)."""
-    import numpy as np
-    if hasattr(a, "is_cuda") and a.is_cuda:
-        import torch
-        if a.dtype != torch.float64:
-            raise ValueError(f"{name} must be float64")
-        a = a.contiguous()
-        if tuple(a.shape) != (n,) + shape_tail:
-            raise ValueError(f"{name} has shape {tuple(a.shape)}, expected {(n,) + shape_tail}")
-        return a, _lib.ptr(a, _lib._d), True
-    x = np.ascontiguousarray(np.asarray(a), dtype=np.float64)
-    if shape_tail == () and x.ndim != 1:
-        x = x.reshape(-1)
-    if x.shape != (n,) + shape_tail:
-        raise ValueError(f"{name} has shape {x.shape}, expected {(n,) + shape_tail}")
-    return x, _lib.ptr(x, _lib._d), False
 
 
 def project2d_f64(positions, h, a0, a1=None, *, projection_axis=2, image_size, extent,
@@ -236,66 +160,40 @@ def project2d_f64(positions, h, a0, a1=None, *, projection_axis=2, image_size, e
     buffers, maps left on ``device`` -- e.g. for an RCCL sum), else NumPy arrays."""
     import numpy as np
     import torch
-    from ._axes import axis_index
-    if isinstance(projection_axis, tuple):  # (pixel axis, cull axis): reference_axes()
-        axis = int(projection_axis[0])
-        if int(projection_axis[1]) != axis:
-            axis |= (int(projection_axis[1]) + 1) << 4  # ASP_AXIS_CULL
-    else:
-        axis = axis_index(projection_axis)
-    n = int(positions.shape[0])
-    keep = []
-    pos, ppos, on_dev = _f64_arg(positions, "positions", n, (3,))
-    keep.append(pos)
-    ptrs = [ppos]
-    for arr, name in ((h, "smoothing_lengths"), (a0, "a0"), (a1, "a1")):
-        if arr is None:
-            ptrs.append(None)
-            continue
-        x, px, d = _f64_arg(arr, name, n)
-        if d != on_dev:
-            raise ValueError("positions and fields must all be host arrays or all device tensors")
-        keep.append(x)
-        ptrs.append(px)
-    nx, ny = int(image_size[0]), int(image_size[1])
-    nout = 1 if a1 is None else 2
-    flags = (_lib.ASP_F_RATIO if ratio else 0) | (_lib.ASP_F_ACCUMULATE if accumulate else 0) | \
-        (_lib.ASP_F_DETERMINISTIC if deterministic else 0)
+    axis = axis_code(projection_axis)
+    on_dev = is_device(positions)
+    fields = ((h, "smoothing_lengths"), (a0, "a0"), (a1, "a1"))
+    if any(a is not None and is_device(a) != on_dev for a, _ in fields):
+        raise ValueError("positions and fields must all be host arrays or all device tensors")
     if on_dev:
-        dev = pos.device
+        dev = positions.device
         device = dev.index or 0
-        flags |= _lib.ASP_F_DEVICE_PTRS
-        if out0 is None:
-            out0 = torch.empty((nx, ny), dtype=torch.float32, device=dev)
-        if nout == 2 and out1 is None:
-            out1 = torch.empty((nx, ny), dtype=torch.float32, device=dev)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev).cuda_stream
-    elif device_out:
-        _lib.require_gpu(device)
-        flags |= _lib.ASP_F_DEVICE_OUTPUTS
-        dev = torch.device("cuda", device)
-        if out0 is None:
-            out0 = (torch.zeros if accumulate else torch.empty)((nx, ny), dtype=torch.float32, device=dev)
-        if nout == 2 and out1 is None:
-            out1 = (torch.zeros if accumulate else torch.empty)((nx, ny), dtype=torch.float32, device=dev)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev).cuda_stream
+        with stream_scope(dev, stream) as scope:  # any .contiguous() copy on the call's stream
+            pos, n, _ = positions_f64(positions, cast=True)
+            hh, b0, b1 = (None if a is None else dev_f64(a, name, (n,), dev) for a, name in fields)
+            scope.keep(pos, hh, b0, b1)
+        stream = scope.raw
     else:
+        pos, n, _ = positions_f64(positions, cast=True)
+        hh, b0, b1 = (None if a is None else host_f64(a, name, (n,), cast=True, flat=True)
+                      for a, name in fields)
         _lib.require_gpu(device)
-        if out0 is None:
-            out0 = np.zeros((nx, ny), dtype=np.float32)
-        if nout == 2 and out1 is None:
-            out1 = np.zeros((nx, ny), dtype=np.float32)
-    for t in (out0, out1):
-        if t is not None and (t.dtype not in (np.float32, torch.float32) or int(np.prod(t.shape)) != nx * ny):
-            raise ValueError("outputs must be float32 (nx, ny) arrays")
+        dev = torch.device("cuda", device) if device_out else None
+        if dev is not None or stream is not None:
+            stream = raw_stream(stream, dev)
+    nx, ny = int(image_size[0]), int(image_size[1])
+    dtype = np.float32 if dev is None else torch.float32
+    zeros = dev is None or (accumulate and not on_dev)  # (a fresh device_out map is summed into)
+    out0 = alloc_out((nx, ny), dtype, dev, out0, zeros=zeros)
+    if a1 is not None or out1 is not None:
+        out1 = alloc_out((nx, ny), dtype, dev, out1, zeros=zeros)
     x_min, x_max, y_min, y_max = (float(np.asarray(e)) for e in extent)
     _lib.check(_lib.lib().asp_project2d_f64(
-        ptrs[0], ptrs[1], ptrs[2], ptrs[3], n, axis, x_min, x_max, y_min, y_max, nx, ny,
-        int(chunk_size), kernel_id(kernel), flags, _lib.ptr(out0), _lib.ptr(out1),
-        int(device), stream))
-    return out0, (out1 if nout == 2 else None)
+        dptr(pos), dptr(hh), dptr(b0), dptr(b1), n, axis, x_min, x_max, y_min, y_max, nx, ny,
+        int(chunk_size), kernel_id(kernel),
+        call_flags(on_dev, ratio, accumulate, deterministic, device_out and not on_dev),
+        _lib.ptr(out0), _lib.ptr(out1), int(device), stream))
+    return out0, (out1 if a1 is not None else None)
 
 
 def project3d(x, y, z, h, a, *, cube_size, extent, kernel="cubic", planes=None,
@@ -313,20 +211,12 @@ def project3d(x, y, z, h, a, *, cube_size, extent, kernel="cubic", planes=None,
         _check(t, name, n, dev)
     nx, ny, nz = (int(c) for c in cube_size)
     k_lo, k_hi = (0, nz) if planes is None else (int(planes[0]), int(planes[1]))
-    shape = (nx, ny, max(0, k_hi - k_lo))
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=dev)
-    if (out.dtype != torch.float32 or out.device != dev or not out.is_contiguous()
-            or out.numel() != shape[0] * shape[1] * shape[2]):
-        raise ValueError("out must be a contiguous float32 (nx, ny, k_hi - k_lo) tensor on the device")
-    flags = _lib.ASP_F_DEVICE_PTRS | (_lib.ASP_F_ACCUMULATE if accumulate else 0)
-    if stream is None:
-        stream = torch.cuda.current_stream(dev).cuda_stream
+    out = alloc_out((nx, ny, max(0, k_hi - k_lo)), torch.float32, dev, out, name="out")
     P = _lib.ptr
     e = [float(v) for v in extent]
     _lib.check(_lib.lib().asp_project3d(P(x), P(y), P(z), P(h), P(a), n, *e, nx, ny, nz, k_lo,
-                                        k_hi, kernel_id(kernel), flags, P(out), dev.index or 0,
-                                        stream))
+                                        k_hi, kernel_id(kernel), call_flags(True, accumulate=accumulate),
+                                        P(out), dev.index or 0, raw_stream(stream, dev)))
     return out
 
 

@@ -16,6 +16,7 @@ the map, ``"reduce_scatter"`` for a row-slab-distributed map (each rank keeps nx
 from __future__ import annotations
 
 from . import _lib
+from ._call import raw_stream
 from .device import project2d
 
 
@@ -120,7 +121,7 @@ class PendingMap:
                 else:
                     _lib.check(_lib.lib().asp_ratio(_lib.ptr(o0), _lib.ptr(o1), o0.numel(),
                                                     dev.index or 0,
-                                                    torch.cuda.current_stream(dev).cuda_stream))
+                                                    raw_stream(None, dev)))
             if self._gather is not None:
                 import torch.distributed as dist
                 full, group = self._gather

@@ -13,6 +13,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
+from ._call import alloc_out, call_flags, dptr, is_device, positions_f64, stream_scope
 
 MAX_SETS = 8
 
@@ -52,54 +53,35 @@ def nearest_haloes(positions, centres, box_width, masks=None, *, device: int = 0
     distance inf; -1 and NaN for a position with a non-finite coordinate) and float64
     distances.
     """
-    import torch
-    on_device = hasattr(positions, "is_cuda") and positions.is_cuda
-    if on_device:
-        pos = positions
-        if pos.dtype != torch.float64 or pos.dim() != 2 or pos.shape[1] != 3:
-            raise ValueError("positions must be an (N, 3) float64 tensor")
-        pos = pos.contiguous()
-    else:
-        pos = np.asarray(positions)
-        if pos.ndim != 2 or pos.shape[1] != 3:
-            raise ValueError(f"positions must have shape (N, 3), got {pos.shape}")
-        if pos.dtype != np.float64:
-            raise ValueError(f"positions must be float64, got {pos.dtype}")
-        pos = np.ascontiguousarray(pos)
-    cen = centres.cpu().numpy() if hasattr(centres, "is_cuda") else np.asarray(centres)
-    if cen.ndim != 2 or cen.shape[1] != 3:
-        raise ValueError(f"centres must have shape (M, 3), got {cen.shape}")
-    if cen.dtype != np.float64:
-        raise ValueError(f"centres must be float64, got {cen.dtype}")
-    cen = np.ascontiguousarray(cen)
-    m, n = cen.shape[0], pos.shape[0]
+    on_device = is_device(positions)
+    if not on_device:
+        pos, n, _ = positions_f64(positions, cast=False)
+    cen = positions_f64(centres.cpu() if hasattr(centres, "is_cuda") else centres, "centres",
+                        cast=False)[0]
+    m = cen.shape[0]
     words = None if masks is None else _member_words(list(masks), m)
     nsets = 1 if masks is None else len(masks)
     box_width = float(box_width)
     u32 = _lib.C.POINTER(_lib.C.c_uint32)
     if on_device:
-        dev = pos.device
-        index = torch.empty((nsets, n), dtype=torch.int32, device=dev)
-        distance = torch.empty((nsets, n), dtype=torch.float64, device=dev)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        stream = getattr(stream, "cuda_stream", stream)  # a torch stream or a raw handle
-        ext = torch.cuda.ExternalStream(stream, device=dev)
-        with torch.cuda.stream(ext):  # the centres' upload ordered on the call's stream
+        import torch
+        dev = positions.device
+        with stream_scope(dev, stream) as scope:  # the centres' upload ordered on the call's stream
+            pos, n, _ = positions_f64(positions, cast=False)
             dcen = torch.from_numpy(cen).to(dev)
             dwords = None if words is None else torch.from_numpy(words.view(np.int32)).to(dev)
-        _lib.check(_lib.lib().asp_nearest(
-            _lib.ptr(pos, _lib._d), n, _lib.ptr(dcen, _lib._d), m, _lib.ptr(dwords, u32), nsets,
-            box_width, _lib.ptr(index, _lib._i32), _lib.ptr(distance, _lib._d),
-            _lib.ASP_F_DEVICE_PTRS, dev.index or 0, stream))
-        for t in (dcen, dwords):  # freed by the caching allocator only after the stream's work
-            if t is not None:
-                t.record_stream(ext)
+            scope.keep(pos, dcen, dwords)
+            index = alloc_out((nsets, n), torch.int32, dev)
+            distance = alloc_out((nsets, n), torch.float64, dev)
+            _lib.check(_lib.lib().asp_nearest(
+                dptr(pos), n, dptr(dcen), m, _lib.ptr(dwords, u32), nsets, box_width,
+                _lib.ptr(index, _lib._i32), dptr(distance), call_flags(device_ptrs=True),
+                dev.index or 0, scope.raw))
         return index, distance
     _lib.require_gpu(device)
-    index = np.empty((nsets, n), dtype=np.int32)
-    distance = np.empty((nsets, n), dtype=np.float64)
+    index = alloc_out((nsets, n), np.int32, None)
+    distance = alloc_out((nsets, n), np.float64, None)
     _lib.check(_lib.lib().asp_nearest(
-        _lib.ptr(pos, _lib._d), n, _lib.ptr(cen, _lib._d), m, _lib.ptr(words, u32), nsets,
-        box_width, _lib.ptr(index, _lib._i32), _lib.ptr(distance, _lib._d), 0, device, None))
+        dptr(pos), n, dptr(cen), m, _lib.ptr(words, u32), nsets, box_width,
+        _lib.ptr(index, _lib._i32), dptr(distance), 0, device, None))
     return index, distance

@@ -20,17 +20,12 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
+from ._call import dptr as d, raw_stream, upload_f64
 
 
 def _dev(a):
-    import torch
-    if hasattr(a, "is_cuda") and a.is_cuda:
-        return a.to(torch.float64).contiguous(), False
-    _lib.require_gpu(0)
-    a = np.ascontiguousarray(np.asarray(a), dtype=np.float64)
-    if not a.flags.writeable:  # torch.from_numpy wants a writeable buffer
-        a = a.copy()
-    return torch.from_numpy(a).cuda(), True
+    """(float64 device tensor, was_host): any dtype is cast."""
+    return upload_f64(a, "input", cast=True)
 
 
 class IonisationTable:
@@ -75,8 +70,7 @@ class IonisationTable:
             raise IndexError(f"redshift input index {self._z} is out of bounds for "
                              f"{self._n} table dimensions")
         out = torch.empty(P.shape[0], dtype=torch.float64, device=P.device)
-        d = lambda t: _lib.ptr(t, _lib._d)  # noqa: E731
-        st = torch.cuda.current_stream(P.device).cuda_stream
+        st = raw_stream(None, P.device)
         dev = P.device.index or 0
         if self._n == 3:
             _lib.check(_lib.lib().asp_table_interp3(

@@ -11,6 +11,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
+from ._call import alloc_out, call_flags, dptr, is_device, positions_f64, stream_scope
 
 
 def knn_smoothing_lengths(positions, k: int = 32, *, device: int = 0, stream=None):
@@ -20,24 +21,18 @@ def knn_smoothing_lengths(positions, k: int = 32, *, device: int = 0, stream=Non
     array, or a float64 torch tensor on the GPU, returning a tensor there.  ``inf`` where
     fewer than k particles exist (as scipy reports a missing neighbour).
     """
-    import torch
     k = int(k)
-    if hasattr(positions, "is_cuda") and positions.is_cuda:
-        pos = positions.contiguous()
-        if pos.dtype != torch.float64 or pos.dim() != 2 or pos.shape[1] != 3:
-            raise ValueError("positions must be an (N, 3) float64 tensor")
-        h = torch.empty(pos.shape[0], dtype=torch.float64, device=pos.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(pos.device).cuda_stream
-        _lib.check(_lib.lib().asp_knn_smoothing_lengths(
-            _lib.ptr(pos, _lib._d), pos.shape[0], k, _lib.ptr(h, _lib._d), _lib.ASP_F_DEVICE_PTRS,
-            pos.device.index or 0, stream))
+    if is_device(positions):
+        dev = positions.device
+        with stream_scope(dev, stream) as scope:  # a .contiguous() copy is ordered on the stream
+            pos, n, _ = positions_f64(positions, cast=True)
+            scope.keep(pos)
+            h = alloc_out((n,), pos.dtype, dev)
+            _lib.check(_lib.lib().asp_knn_smoothing_lengths(
+                dptr(pos), n, k, dptr(h), call_flags(device_ptrs=True), dev.index or 0, scope.raw))
         return h
-    pos = np.ascontiguousarray(np.asarray(positions), dtype=np.float64)
-    if pos.ndim != 2 or pos.shape[1] != 3:
-        raise ValueError(f"positions must have shape (N, 3), got {pos.shape}")
+    pos, n, _ = positions_f64(positions, cast=True)
     _lib.require_gpu(device)
-    h = np.empty(pos.shape[0], dtype=np.float64)
-    _lib.check(_lib.lib().asp_knn_smoothing_lengths(_lib.ptr(pos, _lib._d), pos.shape[0], k,
-                                                    _lib.ptr(h, _lib._d), 0, device, None))
+    h = alloc_out((n,), np.float64, None)
+    _lib.check(_lib.lib().asp_knn_smoothing_lengths(dptr(pos), n, k, dptr(h), 0, device, None))
     return h

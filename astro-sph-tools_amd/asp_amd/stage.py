@@ -17,34 +17,13 @@ crosses a box face, so a projection of the staged set over the box is the period
 """
 from __future__ import annotations
 
-import numpy as np
-
 from . import _lib
 from ._axes import axis_index
+from ._call import (call_flags, dev_f64, dptr, host_f64, is_device, positions_f64, raw_stream,
+                    stream_scope)
 
 _SHIFT = {None: 0, "wrap": _lib.ASP_PB_WRAP, "origin": _lib.ASP_PB_SHIFT_ORIGIN,
           "centre": _lib.ASP_PB_SHIFT_CENTRE, "center": _lib.ASP_PB_SHIFT_CENTRE}
-
-
-def _is_device(a):
-    return hasattr(a, "is_cuda") and a.is_cuda
-
-
-def _host_f64(a, name, shape=None):
-    x = np.ascontiguousarray(np.asarray(a), dtype=np.float64)
-    if shape is not None and x.shape != shape:
-        raise ValueError(f"{name} must have shape {shape}, got {x.shape}")
-    return x
-
-
-def _dev_f64(t, name, dev, n):
-    import torch
-    if t.dtype != torch.float64 or t.device != dev:
-        raise ValueError(f"{name} must be a float64 tensor on {dev}")
-    t = t.contiguous()
-    if t.shape[0] != n:
-        raise ValueError(f"{name} has {t.shape[0]} rows, expected {n}")
-    return t
 
 
 def stage_particles(positions, smoothing_lengths=None, *properties, projection_axis=2,
@@ -74,36 +53,28 @@ def stage_particles(positions, smoothing_lengths=None, *properties, projection_a
     if images and smoothing_lengths is None:
         raise ValueError("periodic images need smoothing lengths")
     axis = axis_index(projection_axis)
-    on_dev = _is_device(positions)
+    fields = [(smoothing_lengths, "smoothing_lengths")] + \
+        [(p, f"property {i}") for i, p in enumerate(properties)]
+    on_dev = is_device(positions)
     if on_dev:
         dev = positions.device
-        pos = positions.contiguous()
-        if pos.dtype != torch.float64 or pos.dim() != 2 or pos.shape[1] != 3:
-            raise ValueError("positions must be an (N, 3) float64 tensor")
-        n = pos.shape[0]
-        h = None if smoothing_lengths is None else _dev_f64(smoothing_lengths, "smoothing_lengths", dev, n)
-        props = [_dev_f64(p, f"property {i}", dev, n) for i, p in enumerate(properties)]
-        flags = _lib.ASP_F_DEVICE_PTRS
         device = dev.index or 0
+        with stream_scope(dev, stream) as scope:  # .contiguous() copies ordered on the stream
+            pos, n, _ = positions_f64(positions, cast=True)
+            h, *props = (None if a is None else dev_f64(a, name, (n,), dev, flat=True)
+                         for a, name in fields)
+            scope.keep(pos, h, *props)
+        stream = scope.raw
     else:
-        pos = np.asarray(positions)
-        if pos.ndim != 2 or pos.shape[1] != 3:
-            raise ValueError(f"positions must have shape (N, 3), got {pos.shape}")
-        pos = _host_f64(pos, "positions")
-        n = pos.shape[0]
-        h = None if smoothing_lengths is None else _host_f64(np.asarray(smoothing_lengths).reshape(-1),
-                                                             "smoothing_lengths", (n,))
-        props = [_host_f64(np.asarray(p).reshape(-1), f"property {i}", (n,))
-                 for i, p in enumerate(properties)]
-        flags = 0
+        pos, n, _ = positions_f64(positions, cast=True)
+        h, *props = (None if a is None else host_f64(a, name, (n,), cast=True, flat=True)
+                     for a, name in fields)
         _lib.require_gpu(device)
         dev = torch.device("cuda", device)
-    c = None if centre is None else _host_f64(np.asarray(centre, dtype=np.float64).reshape(-1),
-                                              "centre", (3,))
+        stream = raw_stream(stream, dev)
+    c = None if centre is None else host_f64(centre, "centre", (3,), cast=True, flat=True)
     L = float(box_width) if box_width is not None else 0.0
-    if stream is None:
-        stream = torch.cuda.current_stream(dev).cuda_stream
-    P, Pd = _lib.ptr, (lambda a: _lib.ptr(a, _lib._d))
+    P, Pd, flags = _lib.ptr, dptr, call_flags(device_ptrs=on_dev)
     cap = n if not images else n + max(1024, n // 4)
     while True:
         outs = [torch.empty(max(cap, 1), dtype=torch.float32, device=dev)

@@ -26,6 +26,7 @@ from __future__ import annotations
 import numpy as np
 
 from .. import _lib
+from .._call import alloc_out, call_flags, is_device, stream_scope
 from ._periodic_box_manipulations import _has_units, _in, _wrap
 
 _MODES = {"mapping": _lib.ASP_MATCH_MAPPING, "reorder": _lib.ASP_MATCH_REORDER}
@@ -34,10 +35,6 @@ _NO_DEFAULT = ("More output elements expected than matches but no default value 
                "no output target array to write matches to.")
 _DUPLICATES = ("Duplicate matched detected in filtered source array. Source ID array must contain "
                "unique elements (after optional filter is applied).")
-
-
-def _on_device(x) -> bool:
-    return hasattr(x, "is_cuda") and x.is_cuda
 
 
 def _host_ids(x, name):
@@ -88,13 +85,6 @@ def _device_filter(f, n, name, dev):
     return f.to(dev).contiguous().view(torch.uint8)
 
 
-def _raw_stream(stream, dev):
-    import torch
-    if stream is None:
-        stream = torch.cuda.current_stream(dev)
-    return getattr(stream, "cuda_stream", stream)  # a torch stream or a raw handle
-
-
 def match_ids(source_ids, target_ids, source_filter=None, target_filter=None, *,
               mode="mapping", device: int = 0, stream=None):
     """``(index, source_matched, counts)`` of the module docstring.
@@ -110,27 +100,23 @@ def match_ids(source_ids, target_ids, source_filter=None, target_filter=None, *,
     if mode not in _MODES:
         raise ValueError(f"mode must be 'mapping' or 'reorder', got {mode!r}")
     counts = (_lib.C.c_int64 * 3)()
-    if _on_device(source_ids) or _on_device(target_ids):
+    if is_device(source_ids) or is_device(target_ids):
         import torch
-        dev = source_ids.device if _on_device(source_ids) else target_ids.device
-        raw = _raw_stream(stream, dev)
-        ext = torch.cuda.ExternalStream(raw, device=dev)
-        with torch.cuda.stream(ext):  # conversions and uploads ordered on the call's stream
+        dev = source_ids.device if is_device(source_ids) else target_ids.device
+        with stream_scope(dev, stream) as scope:  # conversions and uploads ordered on the stream
             S = _device_ids(source_ids, "source_ids", dev)
             T = _device_ids(target_ids, "target_ids", dev)
             ns, nt = S.numel(), T.numel()
             sf = _device_filter(source_filter, ns, "source_filter", dev)
             tf = _device_filter(target_filter, nt, "target_filter", dev)
-            index = torch.empty(nt, dtype=torch.int32, device=dev)
-            matched = torch.zeros(ns, dtype=torch.uint8, device=dev)
-        _lib.check(_lib.lib().asp_match_ids(
-            _lib.ptr(S, _lib._i64), _lib.ptr(sf, _lib._u8), ns, _lib.ptr(T, _lib._i64),
-            _lib.ptr(tf, _lib._u8), nt, _MODES[mode], _lib.ptr(index, _lib._i32),
-            _lib.ptr(matched, _lib._u8), counts, _lib.ASP_F_DEVICE_PTRS, dev.index or 0, raw))
-        for t in (S, T, sf, tf, index, matched):
-            if t is not None:
-                t.record_stream(ext)
-        with torch.cuda.stream(ext):
+            index = alloc_out((nt,), torch.int32, dev)
+            matched = alloc_out((ns,), torch.uint8, dev, zeros=True)
+            scope.keep(S, T, sf, tf, index, matched)
+            _lib.check(_lib.lib().asp_match_ids(
+                _lib.ptr(S, _lib._i64), _lib.ptr(sf, _lib._u8), ns, _lib.ptr(T, _lib._i64),
+                _lib.ptr(tf, _lib._u8), nt, _MODES[mode], _lib.ptr(index, _lib._i32),
+                _lib.ptr(matched, _lib._u8), counts, call_flags(device_ptrs=True),
+                dev.index or 0, scope.raw))
             matched = matched.view(torch.bool)
         return index, matched, tuple(int(c) for c in counts)
     S = _host_ids(source_ids, "source_ids")
@@ -161,12 +147,10 @@ def take_rows(data, index, output_array=None, default_value=None, *, device: int
     (uninitialised for a fresh output).  Rows are ``data[i]``: trailing dimensions move as one
     row of bytes.  Host arrays or device tensors (``data`` decides); an ``index >= len(data)``
     raises ValueError.  Returns the output."""
-    if _on_device(data):
+    if is_device(data):
         import torch
         dev = data.device
-        raw = _raw_stream(stream, dev)
-        ext = torch.cuda.ExternalStream(raw, device=dev)
-        with torch.cuda.stream(ext):
+        with stream_scope(dev, stream) as scope:
             src = data.contiguous()
             idx = index if hasattr(index, "is_cuda") else torch.from_numpy(
                 np.ascontiguousarray(index, dtype=np.int32))
@@ -178,7 +162,7 @@ def take_rows(data, index, output_array=None, default_value=None, *, device: int
             out = output_array
             if out is None:
                 out = torch.empty((n_index,) + row_shape, dtype=src.dtype, device=dev)
-            elif (not _on_device(out) or out.dtype != src.dtype or not out.is_contiguous()
+            elif (not is_device(out) or out.dtype != src.dtype or not out.is_contiguous()
                   or tuple(out.shape) != (n_index,) + row_shape):
                 raise ValueError("output_array must be a contiguous device tensor of the data's "
                                  f"dtype and shape {(n_index,) + row_shape}")
@@ -186,13 +170,11 @@ def take_rows(data, index, output_array=None, default_value=None, *, device: int
             if default_value is not None:
                 fill = torch.as_tensor(default_value, dtype=src.dtype, device=dev)
                 fill = fill.broadcast_to(row_shape).contiguous()
-        row_bytes = src.element_size() * int(np.prod(row_shape, dtype=np.int64))
-        _lib.check(_lib.lib().asp_take_rows(
-            _void(src), src.shape[0], row_bytes, _lib.ptr(idx, _lib._i32), n_index, _void(fill),
-            _void(out), _lib.ASP_F_DEVICE_PTRS, dev.index or 0, raw))
-        for t in (src, idx, fill, out):
-            if t is not None:
-                t.record_stream(ext)
+            scope.keep(src, idx, fill, out)
+            row_bytes = src.element_size() * int(np.prod(row_shape, dtype=np.int64))
+            _lib.check(_lib.lib().asp_take_rows(
+                _void(src), src.shape[0], row_bytes, _lib.ptr(idx, _lib._i32), n_index,
+                _void(fill), _void(out), call_flags(device_ptrs=True), dev.index or 0, scope.raw))
         return out
     src = np.ascontiguousarray(data)
     if src.ndim < 1:

@@ -21,6 +21,7 @@ from __future__ import annotations
 import numpy as np
 
 from .. import _lib
+from .._call import dptr as P, raw_stream, upload_f64
 
 
 def _has_units(x) -> bool:
@@ -37,18 +38,6 @@ def _wrap(like, values, units):
     return type(like)(values, units=units)
 
 
-def _prep(x):
-    """(device float64 tensor, was_numpy)."""
-    import torch
-    if hasattr(x, "is_cuda") and x.is_cuda:
-        if x.dtype != torch.float64:
-            raise ValueError("device tensors must be float64")
-        return x.contiguous(), False
-    a = np.ascontiguousarray(np.asarray(x), dtype=np.float64)
-    _lib.require_gpu(0)
-    return torch.from_numpy(a).to("cuda"), True
-
-
 def _period(t, shape):
     """Elements after which a broadcast operand repeats in C order, or None."""
     full = int(np.prod(shape)) if len(shape) else 1
@@ -61,18 +50,17 @@ def _period(t, shape):
 
 def _run(op, a, b, box_width, origin_is_centre=False):
     import torch
-    ta, na = _prep(a)
-    tb, nb = _prep(b) if b is not None else (None, True)
+    ta, na = upload_f64(a, "positions")
+    tb, nb = upload_f64(b, "positions") if b is not None else (None, True)
     shape = torch.broadcast_shapes(ta.shape, tb.shape) if tb is not None else ta.shape
     ta, pa = _period(ta, shape)
     pb = 1
     if tb is not None:
         tb, pb = _period(tb, shape)
     out = torch.empty(shape, dtype=torch.float64, device=ta.device)
-    P = lambda t: _lib.ptr(t, _lib._d)  # noqa: E731
     _lib.check(_lib.lib().asp_periodic(
         op, P(ta), pa, P(tb), pb, out.numel(), float(box_width), int(bool(origin_is_centre)),
-        P(out), ta.device.index or 0, torch.cuda.current_stream(ta.device).cuda_stream))
+        P(out), ta.device.index or 0, raw_stream(None, ta.device)))
     return out.cpu().numpy() if (na and nb) else out
 
 
@@ -96,8 +84,8 @@ def calculate_wrapped_distance(from_position, to_positions, box_width,
         d = calculate_wrapped_distance(_in(from_position, u), to_positions.value,
                                        _in(box_width, u), do_squared_distance)
         return _wrap(to_positions, d, u ** 2 if do_squared_distance else u)
-    tf, nf = _prep(from_position)
-    tt, nt = _prep(to_positions)
+    tf, nf = upload_f64(from_position, "from_position")
+    tt, nt = upload_f64(to_positions, "to_positions")
     shape = torch.broadcast_shapes(tf.shape, tt.shape)
     if len(shape) not in (1, 2) or shape[-1] != 3:
         raise ValueError(f"positions must be (3,) or (N, 3), got {tuple(shape)}")
@@ -105,10 +93,9 @@ def calculate_wrapped_distance(from_position, to_positions, box_width,
     tt, pt = _period(tt, shape)
     rows = 1 if len(shape) == 1 else shape[0]
     out = torch.empty(rows, dtype=torch.float64, device=tf.device)
-    P = lambda t: _lib.ptr(t, _lib._d)  # noqa: E731
     _lib.check(_lib.lib().asp_wrapped_distance(
         P(tf), pf, P(tt), pt, rows, float(box_width), int(bool(do_squared_distance)), P(out),
-        tf.device.index or 0, torch.cuda.current_stream(tf.device).cuda_stream))
+        tf.device.index or 0, raw_stream(None, tf.device)))
     if len(shape) == 1:
         return np.float64(out.item()) if (nf and nt) else out[0]
     return out.cpu().numpy() if (nf and nt) else out

@@ -20,6 +20,7 @@ from __future__ import annotations
 import numpy as np
 
 from ... import _lib
+from ..._call import positions_f64
 from ._kernels import COLUMN_KERNEL_IDS, native_kernel_id, quartic_spline_kernel
 
 
@@ -29,10 +30,7 @@ def create_cube(positions: np.ndarray, smoothing_lengths: np.ndarray,
                 kernel_func=quartic_spline_kernel, *, planes=None, device: int = 0,
                 dtype=np.float64) -> np.ndarray:
     """Deposit particle property A onto an (Nx, Ny, Nz) voxel grid."""
-    pos = np.asarray(positions)
-    if pos.ndim != 2 or pos.shape[1] != 3:
-        raise ValueError(f"positions must have shape (N, 3), got {pos.shape}")
-    n = pos.shape[0]
+    pos, n, _ = positions_f64(positions, cast=True)
     h = np.asarray(smoothing_lengths).reshape(-1)
     A = np.asarray(particle_properties).reshape(-1)
     if h.shape[0] != n or A.shape[0] != n:

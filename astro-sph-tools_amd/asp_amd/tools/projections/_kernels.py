@@ -88,6 +88,47 @@ KERNELS = {k.kernel_id: k for k in (quartic_spline_kernel, wendland_c2_kernel, i
                                     cubic_spline_column_kernel, wendland_c2_column_kernel)}
 COLUMN_KERNEL_IDS = (_lib.ASP_KERNEL_CUBIC_SPLINE_COLUMN, _lib.ASP_KERNEL_WENDLAND_C2_COLUMN)
 
+# The one table of kernel names: each kernel object's __name__, with and without "_kernel",
+# and the short spellings of the cubic spline.
+KERNEL_IDS = {"cubic": _lib.ASP_KERNEL_CUBIC_SPLINE, "cubic_spline": _lib.ASP_KERNEL_CUBIC_SPLINE,
+              "cubic_column": _lib.ASP_KERNEL_CUBIC_SPLINE_COLUMN}
+for _k in KERNELS.values():
+    KERNEL_IDS[_k.__name__] = KERNEL_IDS[_k.__name__[:-len("_kernel")]] = _k.kernel_id
+# the names the device-tensor entry points (asp_amd.device) have always taken
+DEVICE_KERNEL_NAMES = ("cubic", "quartic_spline_kernel", "cubic_spline", "wendland_c2", "indicator",
+                       "cubic_column", "wendland_c2_column")
+
+
+
+def device_kernel_id(kernel) -> int:
+    """One of the three lookups over KERNEL_IDS, one per family of entry points, each with the
+    failure its callers (and their tests) rely on:
+
+    * ``device_kernel_id`` (asp_amd.device): an int passes through unchecked (the C-ABI
+      refuses a bad id), a str outside DEVICE_KERNEL_NAMES is a KeyError, anything else goes
+      to ``native_kernel_id``;
+    * ``named_kernel_id`` (sightline_columns): an SPHKernel or any name of KERNEL_IDS, else a
+      ValueError listing the names;
+    * ``kernel_id_of`` / ``native_kernel_id`` (create_image and the other ``kernel_func=``
+      mirrors of the reference): an SPHKernel of this package; any other callable is None
+      (the plug-in path) / a TypeError; a non-callable is a TypeError.
+    """
+    if isinstance(kernel, int):
+        return kernel
+    if isinstance(kernel, str):
+        if kernel not in DEVICE_KERNEL_NAMES:
+            raise KeyError(kernel)
+        return KERNEL_IDS[kernel]
+    return native_kernel_id(kernel)
+
+
+def named_kernel_id(kernel) -> int:
+    if isinstance(kernel, SPHKernel):
+        return kernel.kernel_id
+    if isinstance(kernel, str) and kernel in KERNEL_IDS:
+        return KERNEL_IDS[kernel]
+    raise ValueError(f"kernel {kernel!r} is not one of {sorted(KERNEL_IDS)} or an SPHKernel")
+
 
 def kernel_id_of(kernel_func):
     """The C-ABI kernel id of one of this package's kernels, or None for any other

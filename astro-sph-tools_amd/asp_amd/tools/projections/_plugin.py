@@ -33,6 +33,8 @@ import ctypes as C
 import numpy as np
 
 from ... import _lib
+from ..._axes import axis_code
+from ..._call import host_f64
 
 TILE = 64
 MAX_PAIRS = 1 << 25  # pairs per emit (12 B each on the host)
@@ -46,12 +48,11 @@ class _Session:
         self.ntx, self.nty = -(-self.nx // TILE), -(-self.ny // TILE)
         self.tile_pairs = np.zeros(self.ntx * self.nty, np.int64)
         self._keep = (pos, h)
-        axis_code = int(axes[0]) | (((int(axes[1]) + 1) << 4) if axes[1] != axes[0] else 0)
         self._h = C.c_void_p()
         L = _lib.lib()
         _lib.check(L.asp_pairs_begin(
-            _lib.ptr(pos, _lib._d), _lib.ptr(h, _lib._d), h.size, axis_code, *extent, self.nx,
-            self.ny, int(chunk_size), 0, device, None, _lib.ptr(self.tile_pairs, _lib._i64),
+            _lib.ptr(pos, _lib._d), _lib.ptr(h, _lib._d), h.size, axis_code(tuple(axes)), *extent,
+            self.nx, self.ny, int(chunk_size), 0, device, None, _lib.ptr(self.tile_pairs, _lib._i64),
             C.byref(self._h)))
 
     def emit(self, t0, t1):
@@ -98,17 +99,11 @@ def project_callable(positions, smoothing_lengths, props, axes, image_size, chun
     if max_pairs is None:
         max_pairs = MAX_PAIRS
     nx, ny = int(image_size[0]), int(image_size[1])
-    pos = np.ascontiguousarray(np.asarray(positions, dtype=np.float64))
-    h = np.ascontiguousarray(np.asarray(smoothing_lengths, dtype=np.float64).reshape(-1))
-    props = [np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1)) for a in props]
     # the session reads h.size rows of positions: every array must describe the same particles
-    # (the native path's checks, device._f64_arg)
-    if pos.ndim != 2 or pos.shape != (h.size, 3):
-        raise ValueError(f"positions must be (N, 3) with N = len(smoothing_lengths) = {h.size}, "
-                         f"got {pos.shape}")
-    for a in props:
-        if a.size != h.size:
-            raise ValueError(f"property of {a.size} values for {h.size} particles")
+    # (the native path's checks, device.project2d_f64)
+    h = host_f64(smoothing_lengths, "smoothing_lengths", cast=True, flat=True)
+    pos = host_f64(positions, "positions", (h.size, 3), cast=True)
+    props = [host_f64(a, "property", (h.size,), cast=True, flat=True) for a in props]
     ext = tuple(float(np.asarray(e)) for e in extent)
     with _Session(pos, h, axes, ext, (nx, ny), chunk_size, device) as S:
         if mode == "per_pixel":

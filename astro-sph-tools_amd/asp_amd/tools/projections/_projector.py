@@ -24,18 +24,19 @@ import numpy as np
 
 from ... import _lib
 from ..._axes import reference_axes
+from ..._call import host_f64, positions_f64
 from ._kernels import kernel_id_of, native_kernel_id, quartic_spline_kernel
 
 
 def _lengths(positions, smoothing_lengths, *fields):
-    pos = np.asarray(positions)
-    if pos.ndim != 2 or pos.shape[1] != 3:
-        raise ValueError(f"positions must have shape (N, 3), got {pos.shape}")
-    n = pos.shape[0]
+    """The positions as the (N, 3) float64 array the native calls take, once every field
+    is known to be N long."""
+    pos, n, _ = positions_f64(positions, cast=True)
     lens = [np.asarray(f).reshape(-1).shape[0] for f in (smoothing_lengths,) + fields]
     if any(k != n for k in lens):
         raise ValueError(f"positions ({n}), smoothing_lengths ({lens[0]}) and "
                          f"particle_properties ({lens[1]}) differ in length")
+    return pos
 
 
 def _check_chunk_size(chunk_size):
@@ -60,10 +61,7 @@ def _run(positions, smoothing_lengths, props, projection_axis, image_size, chunk
         return out0, out1
     _lib.require_gpu(device)
     from ...device import project2d_f64
-    pos = np.asarray(positions)
-    if pos.ndim != 2 or pos.shape[1] != 3:
-        raise ValueError(f"positions must have shape (N, 3), got {pos.shape}")
-    return project2d_f64(pos, smoothing_lengths, props[0], props[1] if len(props) > 1 else None,
+    return project2d_f64(positions, smoothing_lengths, props[0], props[1] if len(props) > 1 else None,
                          projection_axis=reference_axes(projection_axis), image_size=(nx, ny),
                          extent=tuple(float(np.asarray(e)) for e in extent),
                          chunk_size=chunk_size, kernel=kernel_id, ratio=ratio,
@@ -77,10 +75,7 @@ def _run_callable(positions, smoothing_lengths, props, projection_axis, image_si
         return [np.zeros((max(nx, 0), max(ny, 0))) for _ in props]
     _lib.require_gpu(device)
     from ._plugin import project_callable
-    pos = np.asarray(positions)
-    if pos.ndim != 2 or pos.shape[1] != 3:
-        raise ValueError(f"positions must have shape (N, 3), got {pos.shape}")
-    return project_callable(pos, smoothing_lengths, props, reference_axes(projection_axis),
+    return project_callable(positions, smoothing_lengths, props, reference_axes(projection_axis),
                             (nx, ny), chunk_size, extent, kernel_func, device=device, mode=mode,
                             deterministic=deterministic)
 
@@ -102,7 +97,7 @@ def create_image(positions: np.ndarray, smoothing_lengths: np.ndarray,
     """
     cs = _check_chunk_size(chunk_size)
     kid = kernel_id_of(kernel_func)
-    _lengths(positions, smoothing_lengths, particle_properties)
+    positions = _lengths(positions, smoothing_lengths, particle_properties)
     if kid is None:  # an arbitrary Python kernel: the plugin path (_plugin.py)
         img, = _run_callable(positions, smoothing_lengths, [particle_properties],
                              projection_axis, image_size, cs, (x_min, x_max, y_min, y_max),
@@ -136,11 +131,9 @@ def create_weighted_image(positions, smoothing_lengths, weights, values, image_s
         raise ValueError("deterministic=True cannot form a weighted (ratio) map with a native "
                          "kernel: use deterministic=False, or pass the kernel as a plain "
                          "Python callable (the kernel_func plug-in sums in fp64, in order)")
-    _lengths(positions, smoothing_lengths, weights)
-    w = np.asarray(weights, dtype=np.float64).reshape(-1)
-    vals = np.asarray(values, dtype=np.float64).reshape(-1)
-    if vals.shape[0] != w.shape[0]:
-        raise ValueError("values and positions differ in length")
+    positions = _lengths(positions, smoothing_lengths, weights)
+    w = host_f64(weights, "weights", cast=True, flat=True)
+    vals = host_f64(values, "values", (w.shape[0],), cast=True, flat=True)
     ext = (x_min, x_max, y_min, y_max)
     if kid is None:  # an arbitrary Python kernel: the plugin path (_plugin.py)
         s0, s1 = _run_callable(positions, smoothing_lengths, [w * vals, w], projection_axis,
@@ -174,17 +167,16 @@ def create_images(positions, smoothing_lengths, particle_properties, image_size,
     import torch
     cs = _check_chunk_size(chunk_size)
     kid = native_kernel_id(kernel_func)
-    props = [np.asarray(a, dtype=np.float64).reshape(-1) for a in particle_properties]
+    props = [host_f64(a, "particle_properties", cast=True, flat=True) for a in particle_properties]
     if not 1 <= len(props) <= 6:
         raise ValueError("particle_properties: 1 .. 6 arrays")
-    for a in props:
-        _lengths(positions, smoothing_lengths, a)
+    positions = _lengths(positions, smoothing_lengths, *props)
     nx, ny = int(image_size[0]), int(image_size[1])
     if nx <= 0 or ny <= 0 or cs < 0:
         return [np.zeros((max(nx, 0), max(ny, 0)), dtype=dtype) for _ in props]
     _lib.require_gpu(device)
     from ...device import project2d_props_f64
-    maps = project2d_props_f64(np.asarray(positions), smoothing_lengths, props,
+    maps = project2d_props_f64(positions, smoothing_lengths, props,
                                projection_axis=reference_axes(projection_axis),
                                image_size=(nx, ny),
                                extent=tuple(float(np.asarray(e)) for e in (x_min, x_max, y_min, y_max)),

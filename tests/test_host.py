@@ -153,7 +153,7 @@ def test_zslab_bounds_equal_count():
 
 def test_plugin_argument_lengths():
     """The plug-in session reads len(h) rows of positions: mismatched arrays are a
-    ValueError before any native call (as the native path's device._f64_arg checks)."""
+    ValueError before any native call (as the native path's _call.host_f64 checks)."""
     from asp_amd.tools.projections._plugin import project_callable
     f = lambda r, h: r  # noqa: E731
     pos = np.zeros((10, 3))
