@@ -106,6 +106,11 @@ PROTOTYPES = {
 RESTYPES = {"asp_last_error": C.c_char_p}  # every other function returns int
 # Every symbol include/asp.h declares (tests check the library exports all of them).
 EXPORTS = tuple(PROTOTYPES)
+# The C-ABI of include/asp_points.h (the 3-D point sampler), kept apart from the table of asp.h.
+POINT_PROTOTYPES = {
+    "asp_sample3d": [_f] * 6 + [_Q, _d, _d, _d, _Q, _I, _I, _f, _f, _I, _V],
+    "asp_sample3d_f64": [_d] * 4 + [_Q, _d, _d, _d, _Q, _I, _I, _f, _f, _I, _V],
+}
 
 
 class ASPError(RuntimeError):
@@ -132,7 +137,7 @@ def lib():
         except Exception:
             pass
     L = C.CDLL(LIB_PATH)
-    for name, argtypes in PROTOTYPES.items():
+    for name, argtypes in {**PROTOTYPES, **POINT_PROTOTYPES}.items():
         fn = getattr(L, name, None)  # (absent from an older A/B build, ASP_LIB)
         if fn is not None:
             fn.argtypes, fn.restype = argtypes, RESTYPES.get(name, C.c_int)

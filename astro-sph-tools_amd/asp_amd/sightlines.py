@@ -33,8 +33,10 @@ def sightline_columns(positions, smoothing_lengths, particle_properties, points,
 
     ``points``: (M, 2) in projected (u, v) order -- X -> (y, z), Y -> (x, z), Z -> (x, y) --
     or (M, 3) box positions such as ``get_sightline_start_position``, reduced with the same
-    axis selection as the particles.  The sightline runs ALONG ``projection_axis``; a
-    direction vector that is not along it is out of scope (rotate the particles first).
+    axis selection as the particles.  The sightline runs ALONG ``projection_axis`` and the
+    result is its total column; for a direction vector that is not along an axis, or for the
+    run of a field along the sightline, use ``asp_amd.sightline_profiles`` (3-D sums at the
+    centres of the sightline's bins).
 
     ``kernel``: an ``SPHKernel`` or its name ("cubic_column", "wendland_c2_column",
     "quartic_spline", "wendland_c2", "indicator", ...).  With a column kernel the result is a

@@ -140,6 +140,9 @@ enum SampleBuf {
     kSmpScanTmp,               // scan scratch
     kSmpSorted,                // point coordinates in cell order (x, then y)
     kSmpAcc,                   // per-point accumulators (fp64 or int64), in cell order
+    // asp_sample3d / asp_sample3d_f64 (the slots above, and:)
+    kSmpPz,                    // staged third point coordinate
+    kSmpSorted3,               // point coordinates in cell order (x, then y, then z)
     kSampleBufCount
 };
 // Per-call scratch that several entry points reuse, each with its own meaning for slots

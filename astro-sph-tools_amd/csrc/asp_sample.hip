@@ -49,10 +49,10 @@
 #include "asp_host.hpp"
 #include "asp_map_device.hpp"
 #include "asp_prims.hpp"
+#include "asp_sample.hpp"
 
 namespace asp {
 
-constexpr int kSBlock = 256;
 constexpr int kSampleMaxG = 2048;     // cells per axis at most: a 16 MiB cell-start table
 constexpr int kSamplePerCell = 4;     // points per cell the grid aims at
 constexpr int kSampleWideCells = 16;  // boxes over more cells go to the wave (ASP_SAMPLE_WIDE_CELLS)
@@ -67,27 +67,6 @@ struct SDesc {
     int k[2];                             // fixed-point scale exponents
     unsigned long long pairs;             // ASP_SAMPLE_COUNT
 };
-
-// fp64 <-> unsigned with the same order (for atomicMin / atomicMax).
-__device__ __forceinline__ unsigned long long enc_ordered(double d) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(d);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double dec_ordered(unsigned long long e) {
-    const unsigned long long b = (e >> 63) ? (e & 0x7fffffffffffffffull) : ~e;
-    return __longlong_as_double((long long)b);
-}
-
-// Cell of a coordinate along one axis: min(G - 1, max(0, floor((c - c0) s))), monotone
-// non-decreasing in c (a subtraction, a multiplication by s >= 0 and a floor), the same
-// expression for the points and for the particles' box edges.  A NaN product (0 * inf when
-// the box is degenerate) gives cell 0.
-__device__ __forceinline__ int scell(double c, double c0, double s, int G) {
-    double f = floor((c - c0) * s);
-    if (!(f >= 0.0)) f = 0.0;
-    if (f > (double)(G - 1)) f = (double)(G - 1);
-    return (int)f;
-}
 
 __global__ void k_sinit(SDesc* D) {
     D->emin[0] = D->emin[1] = ~0ull;
@@ -239,22 +218,9 @@ __global__ __launch_bounds__(kSBlock) void k_scmax(const SPart P, long long n,
     }
 }
 
-// Fixed-point exponent: every scaled term stays below 2^50 (f2fix needs < 2^51) and a sum
-// of n of them below 2^62, each with a factor 16 to spare for |f| > 1 (a negative h gives
-// q < 0, where the cubic's polynomial reaches 11).  It depends on n and max |c| only, so
-// the sums do not depend on the order of the particles or of the points.
+// The fixed-point exponents (fix_exponent, asp_sample.hpp) from n and max |c|.
 __global__ void k_sscale(SDesc* D, long long n) {
-    for (int j = 0; j < 2; ++j) {
-        const float cm = __uint_as_float(D->cmax[j]);
-        int k = 0;
-        if (cm > 0.0f && n > 0) {
-            int es, et;
-            frexp((double)n * (double)cm, &es);
-            frexp((double)cm, &et);
-            k = min(58 - es, 46 - et);
-        }
-        D->k[j] = k;
-    }
+    for (int j = 0; j < 2; ++j) D->k[j] = fix_exponent(n, __uint_as_float(D->cmax[j]));
 }
 
 // One (particle, point) pair: the reference's test, and the term if it passes.
@@ -362,20 +328,6 @@ __global__ __launch_bounds__(kSBlock) void k_sample(const SPart P, long long n,
             tested += (unsigned long long)__shfl_xor((long long)tested, o);
         if (lane == 0 && tested) atomicAdd(pairs, tested);
     }
-}
-
-// Accumulators (cell order) -> fp32 outputs in the caller's order: emit_pixel, the map's
-// conversion, accumulate and ratio.
-template <int NOUT, int ACC>
-__global__ __launch_bounds__(kSBlock) void k_sfinal(const unsigned long long* __restrict__ acc,
-                                                     long long m, const int* __restrict__ perm,
-                                                     const SDesc* __restrict__ D,
-                                                     float* __restrict__ out0,
-                                                     float* __restrict__ out1, int flags) {
-    const long long j = (long long)blockIdx.x * kSBlock + threadIdx.x;
-    if (j >= m) return;
-    emit_pixel<NOUT, ACC>((long long)perm[j], acc[j], NOUT == 2 ? acc[m + j] : 0ull, D->k[0],
-                          D->k[1], out0, out1, flags);
 }
 
 // The arguments of the two entry points (one of src32 / src64 is set).
@@ -584,7 +536,7 @@ static int sample(const SampleArgs& A, int device, hipStream_t stream) {
         const int kflags = (acc_flag ? kFlagAccumulate : 0) | ((A.flags & ASP_F_RATIO) ? kFlagRatio : 0);
         StageMark mfin(ws, kSSampleDeposit, st);
         ASP_TRY(dispatch(0, nout, det, [&](auto, auto NO, auto AC) -> int {
-            hipLaunchKernelGGL((k_sfinal<decltype(NO)::value, decltype(AC)::value>), dim3(pgrid),
+            hipLaunchKernelGGL((k_sfinal<decltype(NO)::value, decltype(AC)::value, SDesc>), dim3(pgrid),
                                dim3(kSBlock), 0, st, (const unsigned long long*)acc, m, (const int*)iout,
                                (const SDesc*)D, d0, d1, kflags);
             ASP_LAUNCHED();
