@@ -177,12 +177,12 @@ def ptr(a, t=_f):
 
 
 def last_stats(device: int = 0):
-    s = (C.c_int64 * 15)()
-    check(lib().asp_last_stats(device, s, 15))
+    s = (C.c_int64 * 16)()
+    check(lib().asp_last_stats(device, s, 16))
     return {"records": s[0], "items": s[1], "wide": s[2], "tile": s[3], "tiles": s[4],
             "records_per_item": s[5], "merges": s[6], "slabs": s[7], "large": s[8],
             "evals": s[9], "evals_small": s[10], "evals_gather": s[11], "evals_wide": s[12],
-            "scatter_path": s[13], "placement_runs": s[14]}
+            "scatter_path": s[13], "placement_runs": s[14], "layout_reuse": s[15]}
 
 
 def profile(device: int = 0, enable: bool = True, stages=None):

@@ -128,14 +128,25 @@ enum Ctr {
     cRecs = 1,      // records (K2b)
     cWideCount = 2, // wide particles (K1)
     cChunk = 3,     // records per item (K2b)
+    // the four words a scatter writes, adjacent: a pass that reuses the previous layout
+    // zeroes them with one memset and reads them back with one copy
     cWideCursor = 4,// wide list fill (K3)
-    cSlabs = 5,     // int64 partial slabs (K2b)
-    cMerges = 6,    // split tiles (K2b)
-    cWideMax0 = 7,  // max |c0| over wide particles, fp32 bits (K3)
-    cWideMax1 = 8,  // max |c1| over wide particles, fp32 bits (K3)
-    cLarge = 9,     // records in the large stream (K2b)
+    cWideMax0 = 5,  // max |c0| over wide particles, fp32 bits (K3)
+    cWideMax1 = 6,  // max |c1| over wide particles, fp32 bits (K3)
+    cLayoutBad = 7, // verifying scatter (K3): a run did not end where the reused layout says
+    cSlabs = 8,     // int64 partial slabs (K2b)
+    cMerges = 9,    // split tiles (K2b)
+    cLarge = 10,    // records in the large stream (K2b)
     cNum = 16
 };
+constexpr int kScatterWords = 4;  // cWideCursor .. cLayoutBad
+
+// The early return of every kernel behind a verifying scatter (guard: the counter words,
+// or null on a counted pass): the scatter found a run that does not end where the reused
+// layout says, or binned another number of wide particles than the layout's count pass.
+__device__ __forceinline__ bool layout_rejected(const int* __restrict__ guard) {
+    return guard && (guard[cLayoutBad] != 0 || guard[cWideCursor] != guard[cWideCount]);
+}
 
 __device__ __forceinline__ double corner_x(const Grid& g, int xi) {  // xi: window row
     return g.x_min + (double)(xi + g.ox) * g.psx;   // .pyx:13

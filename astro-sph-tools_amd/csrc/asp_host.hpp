@@ -74,7 +74,7 @@ struct Buf {
 };
 
 constexpr int kStages = 23;
-constexpr int kNStats = 15;  // asp_last_stats
+constexpr int kNStats = 16;  // asp_last_stats
 constexpr int kMarks = 8;  // launches of one stage timed per call
 enum Stage {
     kSMemset = 0, kSCount, kSColscan, kSTilescan, kSScatter, kSScale, kSDeposit, kSMerge,
@@ -181,8 +181,43 @@ inline void free_buffers(WorkspaceBufs& bufs) {
     }
 }
 
+// The 2-D map's layout tag ("Layout reuse"): after a counted pass of
+// project2d_device the prefix rows (hist), tile totals and starts, work items, dispatch
+// order, merge list and device counters in the workspace are a function of the particle
+// positions, h and the grid alone, so the next pass over the same particle set may skip
+// its count and scans.  The tag says that those buffers are intact (valid) and what they
+// were made for (key: compared word for word, zero-filled first); the pass that reuses
+// them proves on the device that they are exact for ITS particles (k_scatter, verify), so
+// the key decides only whether the attempt is worth making.
+struct LayoutKey {
+    long long n, nblk, stride;             // particles, count workgroups, Src64::stride
+    double x_min, y_min, psx, psy_pix, psy_cull;  // the window grid (Grid)
+    int nx, ny, cs, gnx, ox, ntiles, nty, nonsquare, mixed;
+    int grp, item_target, item_identity;   // scatter group, deposit items and their order
+    int wide_tiles, gather_min, gather_area;
+    const void* src[5];                    // Src64's fp64 arrays (null: an fp32 caller)
+    const void* pos[3];                    // the pass's u, v, h
+    const void* buf[7];                    // hist, tile_total, tile_start, items, iorder,
+    size_t cap[7];                         // merges, counters: where they are, and their
+                                           // sizes (a re-allocation always grows them)
+};
+constexpr int kLayoutCounters = 7;  // n_recs, n_items, n_merges, n_slabs, n_wide, n_large, chunk
+struct Layout {
+    bool valid = false;
+    LayoutKey key;
+    long long ctr[kLayoutCounters] = {0};  // the counted pass's host counters
+    // Arming (a wasted attempt must be rare): a counted pass arms reuse, a failed attempt
+    // disarms it, and while disarmed a counted pass re-arms it only when its counters
+    // (the last, the records per item, follows from the others) equal the previous
+    // counted pass's -- a caller that rewrites its positions in place pays one wasted scatter.
+    bool armed = true;
+    bool have_last = false;
+    long long last[kLayoutCounters] = {0};
+};
+
 struct Workspace : WorkspaceBufs {
     std::mutex mu;
+    Layout layout;
     // HIP-event profiling (asp_profile): per-stage start/stop events of the last call,
     // folded into the running sums at the next call or at asp_profile_read.
     bool prof = false;

@@ -87,26 +87,33 @@ int launch_count(const Grid& g, const Src64& s, Workspace& ws, const Plan& pl, c
 // rec_cap / wide_cap: the capacities the kernel checks against the device counters (a
 // speculative launch; see project2d_device).  probe: a launch of the placement trials.
 // xa (asp_project2d_props): also write every record's coefficients of properties 2..5
-// (two-map fp64 calls only).
+// (two-map fp64 calls only).  verify: the layout in ws is an earlier call's; the kernel
+// proves it exact for this call's particles or sets the counter word cLayoutBad.
 int launch_scatter(const Grid& g, const Src64& s, Workspace& ws, const Plan& pl, int kid, int nout,
                    bool det, const float* u, const float* v, const float* h, const float* a0,
                    const float* a1, long long rec_cap, int wide_cap, hipStream_t st,
-                   bool probe = false, const XArgs* xa = nullptr);
-int launch_tilescale(const Grid& g, Workspace& ws, const Plan& pl, int nout, hipStream_t st);
+                   bool probe = false, const XArgs* xa = nullptr, bool verify = false);
+// guard (here and in the deposit's launchers): the counter words behind a verifying
+// scatter -- every kernel returns at once when the layout was rejected (layout_rejected) --
+// or null.
+int launch_tilescale(const Grid& g, Workspace& ws, const Plan& pl, int nout, hipStream_t st,
+                     const int* guard = nullptr);
 // asp_map_deposit.hip
 // K4 / K4g / K5 / K6: the records in ws deposited into o0 (, o1) with their own two
 // coefficients (a0 / a1: the properties' fp32 arrays, which the wide particles read
 // directly).
 int launch_deposit(const Grid& g, const Src64& s, Workspace& ws, const Plan& pl, int kid, int nout,
                    bool det, const float* u, const float* v, const float* h, const float* a0,
-                   const float* a1, float* o0, float* o1, int dflags, hipStream_t st);
+                   const float* a1, float* o0, float* o1, int dflags, hipStream_t st,
+                   const int* guard = nullptr);
 // The same for properties (2 pass, 2 pass + 1) of asp_project2d_props (pass = 1, 2), from
 // the coefficients the scatter wrote beside each record (ws.ext); fp64 sums only.
 int launch_deposit_props(const Grid& g, const Src64& s, Workspace& ws, const Plan& pl, int kid,
                          int nout, const float* u, const float* v, const float* h,
                          const float* a0, const float* a1, float* o0, float* o1, int dflags,
                          hipStream_t st, int pass);
-int launch_ratio(float* o0, const float* o1, long long npix, hipStream_t st);  // no StageMark
+int launch_ratio(float* o0, const float* o1, long long npix, hipStream_t st,
+                 const int* guard = nullptr);  // no StageMark
 // ASP_COUNT_EVALS: evals[0..2] += the deposit kernels' lane-slots (k_evals).
 int launch_evals(const Grid& g, const Src64& s, Workspace& ws, const Plan& pl, int kid,
                  const float* u, const float* v, const float* h, unsigned long long* evals,
@@ -128,6 +135,6 @@ int project2d_device(Workspace& ws, const Grid& gin, const Src64& s, const float
                      const float* dv, const float* dh, const float* da0, const float* da1,
                      long long n, int kid, int flags, float* d0, float* d1, hipStream_t st,
                      int* bin_only = nullptr, const XArgs* xa = nullptr, int nxp = 0,
-                     float* const* xo = nullptr);
+                     float* const* xo = nullptr, bool caller_arrays = false);
 
 }  // namespace asp

@@ -168,11 +168,18 @@ __global__ __launch_bounds__(kScatterBlock) void k_scatter(
     Grid g, Src64 s, const int* __restrict__ hist, const long long* __restrict__ tile_start,
     const int* __restrict__ tile_total, float4* __restrict__ recs, unsigned* __restrict__ cmx,
     int* __restrict__ wide_list, int* __restrict__ ctr, int grp, long long rec_cap,
-    int wide_cap, XArgs xa) {
+    int wide_cap, int verify, XArgs xa) {
     // Speculative launch (enqueued before the host has read the counters): the record and
     // wide-list buffers were sized by an earlier call; if this call needs more, every
     // workgroup leaves at once and the host relaunches after growing them.
-    if (ctr[cRecs] > rec_cap || ctr[cWideCount] > wide_cap) return;
+    if (ctr[cRecs] > rec_cap || ctr[cWideCount] > wide_cap) {
+        if (verify && threadIdx.x == 0) atomicOr(&ctr[cLayoutBad], 1);
+        return;
+    }
+    // No record is stored outside the buffer, whatever the cursors say: with a reused
+    // layout (verify) they are the previous call's, and this call's particles may differ.
+    // One unsigned compare: a cursor that wrapped below zero is outside as well.
+    const unsigned slot_cap = (unsigned)min(rec_cap, (long long)0x7fffffff);
     // absolute record cursors: the small / mid-size stream, then the large one
     extern __shared__ __attribute__((aligned(16))) int cur[];
     // per-wave staging for the paired record stores: 64 records x 32 B (second halves
@@ -300,7 +307,8 @@ __global__ __launch_bounds__(kScatterBlock) void k_scatter(
             int tx0 = b.x0 >> kTileShift, tx1 = b.x1 >> kTileShift;
             int ty0 = b.y0 >> kTileShift, ty1 = b.y1 >> kTileShift;
             if ((tx1 - tx0 + 1) * (ty1 - ty0 + 1) > g.wide_tiles) {
-                wide_list[atomicAdd(&ctr[cWideCursor], 1)] = p;
+                const int w = atomicAdd(&ctr[cWideCursor], 1);
+                if ((unsigned)w < (unsigned)wide_cap) wide_list[w] = p;
                 if constexpr (ACC == kAccFix) {
                     atomicMax((unsigned*)&ctr[cWideMax0], c0);
                     if (NOUT == 2) atomicMax((unsigned*)&ctr[cWideMax1], c1);
@@ -324,7 +332,12 @@ __global__ __launch_bounds__(kScatterBlock) void k_scatter(
                 const unsigned bp = tile_box(b, tx, ty);
                 const int col = mb && box_large(bp, g) ? t + g.ntiles : t;
                 int slot = atomicAdd(&cur[col], 1);
-                if constexpr (NX) rec_store(&xa.ext[slot], cx);
+                // (props passes never verify: they scatter after the read-back, ext sized from
+                // the counters, and slot_cap is then no bound; a props pass that reused a
+                // layout would have to pass ext's capacity here)
+                if constexpr (NX) {
+                    if ((unsigned)slot < slot_cap) rec_store(&xa.ext[slot], cx);
+                }
                 if constexpr (ACC == kAccFix) {
                     atomicMax(&cm[t * NOUT], c0);
                     if (NOUT == 2) atomicMax(&cm[t * NOUT + 1], c1);
@@ -332,7 +345,7 @@ __global__ __launch_bounds__(kScatterBlock) void k_scatter(
                 if (first) {
                     first_slot[k] = slot;  // written by the paired store below
                     first_box[k] = bp;
-                } else {
+                } else if ((unsigned)slot < slot_cap) {
                     rec_store(&recs[2 * (long long)slot],
                               make_float4((float)(U - corner_x(g, max(b.x0, tx * kTile))),
                                           (float)(V - corner_y(g, max(b.y0, ty * kTile))),
@@ -371,7 +384,8 @@ __global__ __launch_bounds__(kScatterBlock) void k_scatter(
                 int src = half * 32 + (lane >> 1);
                 int slot = __shfl(first_slot[k], src);
                 float4 val = st[(lane & 1) * 72 + src];
-                if (slot >= 0) rec_store(&recs[2 * (long long)slot + (lane & 1)], val);
+                if ((unsigned)slot < slot_cap)
+                    rec_store(&recs[2 * (long long)slot + (lane & 1)], val);
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             __builtin_amdgcn_wave_barrier();
@@ -399,6 +413,21 @@ __global__ __launch_bounds__(kScatterBlock) void k_scatter(
         unsigned* out = cmx + (long long)blockIdx.x * g.ntiles * NOUT;  // per scatter block
         for (int t = threadIdx.x; t < g.ntiles * NOUT; t += kScatterBlock) out[t] = cm[t];
     }
+    // The proof of a reused layout: every column's cursor stands where this workgroup's
+    // run must end -- where the next scatter workgroup's begins (the prefix row of its
+    // first count workgroup), or at the end of the tile's run for the last one.  Equal for
+    // every (scatter workgroup, column), and the wide count equal (checked behind the
+    // kernel), the layout is the one a count pass over THESE particles makes.
+    if (verify) {
+        const bool last = sb + 1 == gridDim.x;
+        const int* next = hist + (sb + 1) * grp * 2 * g.ntiles;
+        int bad = 0;
+        for (int t = threadIdx.x; t < 2 * g.ntiles; t += kScatterBlock) {
+            const int end = (int)tile_start[t] + (last ? tile_total[t] : next[t]);
+            bad |= cur[t] != end;
+        }
+        if (__syncthreads_or(bad) && threadIdx.x == 0) atomicOr(&ctr[cLayoutBad], 1);
+    }
 }
 
 // ----------------------------------------------------------------------------------
@@ -407,7 +436,9 @@ __global__ __launch_bounds__(kScatterBlock) void k_scatter(
 template <int NOUT>
 __global__ __launch_bounds__(kBlock) void k_tilescale(const unsigned* __restrict__ cmx, int nblk,
                                                       int ntiles, const int* __restrict__ tile_total,
-                                                      int2* __restrict__ tile_k) {
+                                                      int2* __restrict__ tile_k,
+                                                      const int* __restrict__ guard) {
+    if (layout_rejected(guard)) return;
     __shared__ unsigned part[4][64][NOUT];
     int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     int t = blockIdx.x * 64 + lane;
@@ -460,7 +491,7 @@ template <int KID, int NOUT, int ACC, bool CULL, int SRC, int PROBE, int NX>
 static int scatter_variant(const Grid& g, const Src64& s, Workspace& ws, const Plan& pl,
                            const float* u, const float* v, const float* h, const float* a0,
                            const float* a1, long long rec_cap, int wide_cap, hipStream_t st,
-                           const XArgs& xa) {
+                           bool verify, const XArgs& xa) {
     int* dc = (int*)ws.counters.p;
     const size_t lds = scatter_lds(g, NOUT, ACC == kAccFix);
     hipLaunchKernelGGL((k_scatter<KID, NOUT, ACC, CULL, SRC, PROBE, NX>), dim3((unsigned)pl.nblk_s),
@@ -468,7 +499,7 @@ static int scatter_variant(const Grid& g, const Src64& s, Workspace& ws, const P
                        a1, pl.n, pl.nblk, g, s, (const int*)ws.hist.p,
                        (const long long*)ws.tile_start.p, (const int*)ws.tile_total.p,
                        (float4*)ws.recs.p, (unsigned*)ws.cmx.p, (int*)ws.wide.p, dc, pl.grp,
-                       rec_cap, wide_cap, xa);
+                       rec_cap, wide_cap, verify ? 1 : 0, xa);
     ASP_LAUNCHED();
     return ASP_OK;
 }
@@ -476,7 +507,7 @@ static int scatter_variant(const Grid& g, const Src64& s, Workspace& ws, const P
 int launch_scatter(const Grid& g, const Src64& s, Workspace& ws, const Plan& pl, int kid, int nout,
                    bool det, const float* u, const float* v, const float* h, const float* a0,
                    const float* a1, long long rec_cap, int wide_cap, hipStream_t st, bool probe,
-                   const XArgs* xa) {
+                   const XArgs* xa, bool verify) {
     StageMark m(ws, kSScatter, st);
     const XArgs none{};
     ASP_TRY(dispatch(kid, nout, det, [&](auto K, auto N, auto A) {
@@ -486,7 +517,7 @@ int launch_scatter(const Grid& g, const Src64& s, Workspace& ws, const Plan& pl,
                 constexpr int nx = decltype(X)::value;
                 return scatter_variant<K(), N(), A(), decltype(C)::value, decltype(S)::value,
                                        decltype(P)::value, nx>(g, s, ws, pl, u, v, h, a0, a1,
-                                                               rec_cap, wide_cap, st,
+                                                               rec_cap, wide_cap, st, verify,
                                                                nx ? *xa : none);
             };
             return g.nonsquare || g.mixed ? go(std::true_type{}, Int<2>{})
@@ -502,17 +533,18 @@ int launch_scatter(const Grid& g, const Src64& s, Workspace& ws, const Plan& pl,
     return ASP_OK;
 }
 
-int launch_tilescale(const Grid& g, Workspace& ws, const Plan& pl, int nout, hipStream_t st) {
+int launch_tilescale(const Grid& g, Workspace& ws, const Plan& pl, int nout, hipStream_t st,
+                     const int* guard) {
     StageMark m(ws, kSScale, st);
     const dim3 grid((g.ntiles + 63) / 64);
     const unsigned* cmx = (const unsigned*)ws.cmx.p;
     const int* tile_total = (const int*)ws.tile_total.p;
     if (nout == 1)
         hipLaunchKernelGGL((k_tilescale<1>), grid, dim3(kBlock), 0, st, cmx, (int)pl.nblk_s,
-                           g.ntiles, tile_total, (int2*)ws.tile_k.p);
+                           g.ntiles, tile_total, (int2*)ws.tile_k.p, guard);
     else
         hipLaunchKernelGGL((k_tilescale<2>), grid, dim3(kBlock), 0, st, cmx, (int)pl.nblk_s,
-                           g.ntiles, tile_total, (int2*)ws.tile_k.p);
+                           g.ntiles, tile_total, (int2*)ws.tile_k.p, guard);
     ASP_LAUNCHED();
     m.done();
     return ASP_OK;

@@ -666,7 +666,8 @@ __global__ __launch_bounds__(kDepBlock) __attribute__((amdgpu_waves_per_eu(4))) 
     Grid g, Src64 s, const float4* __restrict__ recs, const Item* __restrict__ items,
     const int* __restrict__ order, const int2* __restrict__ tile_k,
     unsigned long long* __restrict__ slabs, float* __restrict__ out0, float* __restrict__ out1,
-    int flags, const float4* __restrict__ ext, int pass) {
+    int flags, const float4* __restrict__ ext, int pass, const int* __restrict__ guard) {
+    if (layout_rejected(guard)) return;
     extern __shared__ __attribute__((aligned(16))) unsigned long long acc[];
     unsigned long long* acc0 = acc;
     unsigned long long* acc1 = acc + kTileWords;
@@ -859,7 +860,8 @@ __global__ __launch_bounds__(kGatherThreads) void k_gather(
     Grid g, Src64 s, const float4* __restrict__ recs, const Item* __restrict__ items,
     const int* __restrict__ order, const int2* __restrict__ tile_k,
     unsigned long long* __restrict__ slabs, float* __restrict__ out0, float* __restrict__ out1,
-    int flags, const float4* __restrict__ ext, int pass) {
+    int flags, const float4* __restrict__ ext, int pass, const int* __restrict__ guard) {
+    if (layout_rejected(guard)) return;
     extern __shared__ __attribute__((aligned(16))) double tot[];
     const Item it = items[order[blockIdx.x / kGatherRegions]];  // largest first
     if (it.mode != 1) return;
@@ -907,7 +909,9 @@ __global__ __launch_bounds__(kBlock) void k_merge(Grid g, const Merge* __restric
                                                   const unsigned long long* __restrict__ slabs,
                                                   const int2* __restrict__ tile_k,
                                                   float* __restrict__ out0,
-                                                  float* __restrict__ out1, int flags) {
+                                                  float* __restrict__ out1, int flags,
+                                                  const int* __restrict__ guard) {
+    if (layout_rejected(guard)) return;
     const Merge m = merges[blockIdx.x];
     int tx = m.tile / g.nty, ty = m.tile - (m.tile / g.nty) * g.nty;
     int X0 = tx * kTile, Y0 = ty * kTile;
@@ -953,7 +957,8 @@ __global__ __launch_bounds__(kGatherThreads) void k_wide(
     Grid g, Src64 s, const float* __restrict__ u, const float* __restrict__ v,
     const float* __restrict__ h, const float* __restrict__ a0, const float* __restrict__ a1,
     const int* __restrict__ wide_list, int n_wide, const int* __restrict__ ctr,
-    float* __restrict__ out0, float* __restrict__ out1) {
+    float* __restrict__ out0, float* __restrict__ out1, const int* __restrict__ guard) {
+    if (layout_rejected(guard)) return;
     extern __shared__ __attribute__((aligned(16))) double tot[];
     const int t = blockIdx.x / kGatherRegions;
     const int tx = t / g.nty, ty = t - (t / g.nty) * g.nty;
@@ -1090,7 +1095,9 @@ __global__ __launch_bounds__(kBlock) void k_evals(Grid g, int kid, Src64 s,
 
 // K7: out0 <- out0 / out1 (0 where out1 == 0).
 __global__ __launch_bounds__(kBlock) void k_ratio(float* __restrict__ out0,
-                                                  const float* __restrict__ out1, long long m) {
+                                                  const float* __restrict__ out1, long long m,
+                                                  const int* __restrict__ guard) {
+    if (layout_rejected(guard)) return;
     long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
     long long stride = (long long)gridDim.x * kBlock;
     for (; i < m; i += stride) {
@@ -1106,7 +1113,7 @@ __global__ __launch_bounds__(kBlock) void k_ratio(float* __restrict__ out0,
 template <int KID, int NOUT, int ACC, int EXT>
 static int run_deposit(const Grid& g, const Src64& s, Workspace& ws, const Plan& pl, const float* u,
                        const float* v, const float* h, const float* a0, const float* a1, float* o0,
-                       float* o1, int dflags, hipStream_t st, int pass) {
+                       float* o1, int dflags, hipStream_t st, int pass, const int* guard) {
     const float4* recs = (const float4*)ws.recs.p;
     const float4* ext = EXT ? (const float4*)ws.ext.p : nullptr;
     const Item* items = (const Item*)ws.items.p;
@@ -1118,7 +1125,8 @@ static int run_deposit(const Grid& g, const Src64& s, Workspace& ws, const Plan&
         const size_t lds = deposit_lds<NOUT>();
         ASP_TRY(allow_dyn_lds((const void*)k_deposit<KID, NOUT, ACC, EXT>, lds));
         hipLaunchKernelGGL((k_deposit<KID, NOUT, ACC, EXT>), dim3(pl.n_items), dim3(kDepBlock), lds,
-                           st, g, s, recs, items, iorder, tile_k, slabs, o0, o1, dflags, ext, pass);
+                           st, g, s, recs, items, iorder, tile_k, slabs, o0, o1, dflags, ext, pass,
+                           guard);
         ASP_LAUNCHED();
         m.done();
     }
@@ -1126,7 +1134,7 @@ static int run_deposit(const Grid& g, const Src64& s, Workspace& ws, const Plan&
         StageMark m(ws, kSGather, st);
         hipLaunchKernelGGL((k_gather<KID, NOUT, ACC, EXT>), dim3(pl.n_items * kGatherRegions),
                            dim3(kGatherThreads), (gather_lds<NOUT, ACC>()), st, g, s, recs, items,
-                           iorder, tile_k, slabs, o0, o1, dflags, ext, pass);
+                           iorder, tile_k, slabs, o0, o1, dflags, ext, pass, guard);
         ASP_LAUNCHED();
         m.done();
     }
@@ -1134,7 +1142,7 @@ static int run_deposit(const Grid& g, const Src64& s, Workspace& ws, const Plan&
         StageMark m(ws, kSMerge, st);
         hipLaunchKernelGGL((k_merge<NOUT, ACC>), dim3(pl.n_merges, kTilePix / kBlock), dim3(kBlock),
                            0, st, g, (const Merge*)ws.merges.p, (const unsigned long long*)slabs,
-                           tile_k, o0, o1, dflags);
+                           tile_k, o0, o1, dflags, guard);
         ASP_LAUNCHED();
         m.done();
     }
@@ -1142,7 +1150,8 @@ static int run_deposit(const Grid& g, const Src64& s, Workspace& ws, const Plan&
         StageMark m(ws, kSWide, st);
         hipLaunchKernelGGL((k_wide<KID, NOUT, ACC>), dim3(g.ntiles * kGatherRegions),
                            dim3(kGatherThreads), (gather_lds<NOUT, ACC>()), st, g, s, u, v, h, a0,
-                           a1, (const int*)ws.wide.p, pl.n_wide, (const int*)ws.counters.p, o0, o1);
+                           a1, (const int*)ws.wide.p, pl.n_wide, (const int*)ws.counters.p, o0, o1,
+                           guard);
         ASP_LAUNCHED();
         m.done();
     }
@@ -1151,9 +1160,11 @@ static int run_deposit(const Grid& g, const Src64& s, Workspace& ws, const Plan&
 
 int launch_deposit(const Grid& g, const Src64& s, Workspace& ws, const Plan& pl, int kid, int nout,
                    bool det, const float* u, const float* v, const float* h, const float* a0,
-                   const float* a1, float* o0, float* o1, int dflags, hipStream_t st) {
+                   const float* a1, float* o0, float* o1, int dflags, hipStream_t st,
+                   const int* guard) {
     return dispatch(kid, nout, det, [&](auto K, auto N, auto A) {
-        return run_deposit<K(), N(), A(), 0>(g, s, ws, pl, u, v, h, a0, a1, o0, o1, dflags, st, 0);
+        return run_deposit<K(), N(), A(), 0>(g, s, ws, pl, u, v, h, a0, a1, o0, o1, dflags, st, 0,
+                                             guard);
     });
 }
 
@@ -1164,14 +1175,15 @@ int launch_deposit_props(const Grid& g, const Src64& s, Workspace& ws, const Pla
     return dispatch_kid(kid, [&](auto K) {
         auto go = [&](auto N) {
             return run_deposit<K(), N(), kAccF64, 1>(g, s, ws, pl, u, v, h, a0, a1, o0, o1, dflags,
-                                                     st, pass);
+                                                     st, pass, nullptr);
         };
         return nout == 2 ? go(Int<2>{}) : go(Int<1>{});
     });
 }
 
-int launch_ratio(float* o0, const float* o1, long long npix, hipStream_t st) {
-    hipLaunchKernelGGL(k_ratio, dim3(stream_blocks(npix)), dim3(kBlock), 0, st, o0, o1, npix);
+int launch_ratio(float* o0, const float* o1, long long npix, hipStream_t st, const int* guard) {
+    hipLaunchKernelGGL(k_ratio, dim3(stream_blocks(npix)), dim3(kBlock), 0, st, o0, o1, npix,
+                       guard);
     ASP_LAUNCHED();
     return ASP_OK;
 }

@@ -201,18 +201,20 @@ static inline int item_target() {
 static inline size_t item_cap(const Grid& g) { return (size_t)2 * g.ntiles + item_target() + kTargetItems1 + 16; }
 static inline size_t merge_cap(const Grid& g) { return (size_t)g.ntiles + 16; }
 
-static int ratio_stage(Workspace& ws, float* o0, const float* o1, long long npix, hipStream_t st) {
+static int ratio_stage(Workspace& ws, float* o0, const float* o1, long long npix, hipStream_t st,
+                       const int* guard = nullptr) {
     StageMark m(ws, kSRatio, st);
-    ASP_TRY(launch_ratio(o0, o1, npix, st));
+    ASP_TRY(launch_ratio(o0, o1, npix, st, guard));
     m.done();
     return ASP_OK;
 }
 
-// K3..K7 for one kernel / map count, on the caller's stream.
+// K3..K7 for one kernel / map count, on the caller's stream.  guard: the counter words
+// behind a verifying scatter (every kernel returns at once when it rejected the layout).
 static int run_tail(const Grid& g, const Src64& s, Workspace& ws, const Plan& pl, int kid, int nout,
                     bool det, const float* u, const float* v, const float* h, const float* a0,
                     const float* a1, float* o0, float* o1, int flags, hipStream_t st,
-                    bool pre_scattered, const XArgs* xa) {
+                    bool pre_scattered, const XArgs* xa, const int* guard = nullptr) {
     const bool ratio = (flags & ASP_F_RATIO) != 0;
     const bool fuse_ratio = ratio && pl.n_wide == 0;
     const int dflags = ((flags & ASP_F_ACCUMULATE) ? kFlagAccumulate : 0) |
@@ -220,10 +222,55 @@ static int run_tail(const Grid& g, const Src64& s, Workspace& ws, const Plan& pl
     if (!pre_scattered)
         ASP_TRY(launch_scatter(g, s, ws, pl, kid, nout, det, u, v, h, a0, a1, kNoRecordCap,
                                0x7fffffff, st, false, xa));
-    if (det) ASP_TRY(launch_tilescale(g, ws, pl, nout, st));
-    ASP_TRY(launch_deposit(g, s, ws, pl, kid, nout, det, u, v, h, a0, a1, o0, o1, dflags, st));
-    if (ratio && !fuse_ratio) ASP_TRY(ratio_stage(ws, o0, o1, (long long)g.nx * g.ny, st));
+    if (det) ASP_TRY(launch_tilescale(g, ws, pl, nout, st, guard));
+    ASP_TRY(launch_deposit(g, s, ws, pl, kid, nout, det, u, v, h, a0, a1, o0, o1, dflags, st,
+                           guard));
+    if (ratio && !fuse_ratio) ASP_TRY(ratio_stage(ws, o0, o1, (long long)g.nx * g.ny, st, guard));
     return ASP_OK;
+}
+
+// ASP_REUSE_LAYOUT=0 (read per call: A/Bs, tests): every pass counts.
+static bool reuse_layout_on() { return env_int("ASP_REUSE_LAYOUT", 1) != 0; }
+
+static LayoutKey layout_key(const Workspace& ws, const Grid& g, const Src64& s, const Plan& pl,
+                            const float* u, const float* v, const float* h) {
+    LayoutKey k;
+    memset(&k, 0, sizeof(k));  // (padding included: keys are compared word for word)
+    k.n = pl.n;
+    k.nblk = pl.nblk;
+    k.stride = s.u64 ? s.stride : 0;
+    k.x_min = g.x_min;
+    k.y_min = g.y_min;
+    k.psx = g.psx;
+    k.psy_pix = g.psy_pix;
+    k.psy_cull = g.psy_cull;
+    k.nx = g.nx;
+    k.ny = g.ny;
+    k.cs = g.cs;
+    k.gnx = g.gnx;
+    k.ox = g.ox;
+    k.ntiles = g.ntiles;
+    k.nty = g.nty;
+    k.nonsquare = g.nonsquare;
+    k.mixed = g.mixed;
+    k.grp = pl.grp;
+    k.item_target = item_target();
+    k.item_identity = item_order_identity();
+    k.wide_tiles = g.wide_tiles;
+    k.gather_min = g.gather_min;
+    k.gather_area = g.gather_area;
+    const void* src[5] = {s.u64, s.v64, s.cu64, s.cv64, s.h64};
+    for (int j = 0; j < 5; ++j) k.src[j] = s.u64 ? src[j] : nullptr;
+    k.pos[0] = u;
+    k.pos[1] = v;
+    k.pos[2] = h;
+    const Buf* buf[7] = {&ws.hist, &ws.tile_total, &ws.tile_start, &ws.items, &ws.iorder,
+                         &ws.merges, &ws.counters};
+    for (int j = 0; j < 7; ++j) {
+        k.buf[j] = buf[j]->p;
+        k.cap[j] = buf[j]->cap;
+    }
+    return k;
 }
 
 // Tunables read once per call (experiments; the defaults are the measured choices).
@@ -231,6 +278,78 @@ static void grid_tunables(Grid& g) {
     g.wide_tiles = (int)env_int("ASP_WIDE_TILES", g.wide_tiles, 1);
     g.gather_min = (int)env_int("ASP_GATHER_MIN", g.gather_min, 2);
     g.gather_area = (int)env_int("ASP_GATHER_AREA", g.gather_area, 4);
+}
+
+// What asp_last_stats reports of a pass (asp.h): the layout's counters, how the records
+// were scattered (path, ntrials) and whether the layout was reused.
+static void pass_stats(Workspace& ws, const Grid& g, const Plan& pl, long long chunk, int path,
+                       int ntrials, int reuse) {
+    ws.stats[0] = pl.n_recs;
+    ws.stats[1] = pl.n_items;
+    ws.stats[2] = pl.n_wide;
+    ws.stats[3] = kTile;
+    ws.stats[4] = g.ntiles;
+    ws.stats[5] = chunk;
+    ws.stats[6] = pl.n_merges;
+    ws.stats[7] = pl.n_slabs;
+    ws.stats[8] = pl.n_large;
+    ws.stats[13] = path;
+    ws.stats[14] = ntrials;
+    ws.stats[15] = reuse;
+}
+
+// A pass on the layout the previous pass left (ws.layout, whose key matches this pass):
+// no count, no scans, no counter read-back.  The scatter runs in its verifying mode and the
+// whole tail is enqueued behind it, every kernel guarded by the scatter's verdict; the host
+// waits only for the copy of the verdict words, made on the side stream while the deposit
+// runs.  outcome 1: the layout was exact for this pass's particles, the maps are written,
+// and the pass is the counted pass's, kernel for kernel.  2: it was not; nothing was
+// written (the outputs are untouched, also under ASP_F_ACCUMULATE), st is idle, and the
+// caller counts.  0: not tried (the record or wide buffers are gone or too small).
+static int reuse_pass(Workspace& ws, const Grid& g, const Src64& s, Plan pl, int kid, int nout,
+                      bool det, const float* du, const float* dv, const float* dh,
+                      const float* da0, const float* da1, float* d0, float* d1, int flags,
+                      hipStream_t st, int& outcome) {
+    outcome = 0;
+    const Layout& L = ws.layout;
+    pl.n_recs = L.ctr[0];
+    pl.n_items = (int)L.ctr[1];
+    pl.n_merges = (int)L.ctr[2];
+    pl.n_slabs = (int)L.ctr[3];
+    pl.n_wide = (int)L.ctr[4];
+    pl.n_large = L.ctr[5];
+    const long long rec_cap = record_capacity(ws);
+    const int wide_cap = (int)std::min<size_t>(ws.wide.cap / sizeof(int), 0x7fffffff);
+    if (!ws.recs.p || !ws.wide.p || !ws.h_counters || pl.n_recs > rec_cap || pl.n_wide > wide_cap)
+        return ASP_OK;
+    ASP_TRY(ensure(ws.slabs, (size_t)pl.n_slabs * nout * kTilePix * sizeof(long long)));
+    ASP_TRY(ensure_side(ws));
+    // The device counters the kernels read (records, wide count) are the counted pass's,
+    // still in place; the words a scatter writes start from zero.
+    int* dc = (int*)ws.counters.p;
+    ASP_HIP(hipMemsetAsync(dc + cWideCursor, 0, kScatterWords * sizeof(int), st));
+    int gate_dev = -1;
+    if (scatter_gate_on() && hipGetDevice(&gate_dev) == hipSuccess) ASP_TRY(gate_wait(gate_dev, st));
+    ASP_TRY(launch_scatter(g, s, ws, pl, kid, nout, det, du, dv, dh, da0, da1, rec_cap, wide_cap,
+                           st, false, nullptr, true));
+    int* hv = ws.h_counters + cNum;  // (the pinned mirror holds kMarks * cNum words)
+    ASP_HIP(hipEventRecord(ws.scan_ev, st));
+    ASP_HIP(hipStreamWaitEvent(ws.side, ws.scan_ev, 0));
+    ASP_HIP(hipMemcpyAsync(hv, dc + cWideCursor, kScatterWords * sizeof(int),
+                           hipMemcpyDeviceToHost, ws.side));
+    ASP_HIP(hipEventRecord(ws.cnt_ev, ws.side));
+    ASP_TRY(run_tail(g, s, ws, pl, kid, nout, det, du, dv, dh, da0, da1, d0, d1, flags, st, true,
+                     nullptr, dc));
+    if (gate_dev >= 0) ASP_TRY(gate_record(gate_dev, st));
+    ASP_HIP(hipEventSynchronize(ws.cnt_ev));
+    outcome = hv[cLayoutBad - cWideCursor] == 0 && hv[0] == pl.n_wide ? 1 : 2;
+    if (outcome == 2) {  // the guarded tail returns at once; the buffers may be re-allocated after it
+        ASP_HIP(hipStreamSynchronize(st));
+        return ASP_OK;
+    }
+    stats_clear(ws);
+    pass_stats(ws, g, pl, L.ctr[6], 1, 0, 1);
+    return ASP_OK;
 }
 
 // The projection on DEVICE arrays (fp32 working copies u, v, h, a0, a1; s: the caller's
@@ -245,10 +364,15 @@ static void grid_tunables(Grid& g) {
 int project2d_device(Workspace& ws, const Grid& gin, const Src64& s, const float* du,
                      const float* dv, const float* dh, const float* da0, const float* da1,
                      long long n, int kid, int flags, float* d0, float* d1, hipStream_t st,
-                     int* bin_only, const XArgs* xa, int nxp, float* const* xo) {
+                     int* bin_only, const XArgs* xa, int nxp, float* const* xo,
+                     bool caller_arrays) {
     Grid g = gin;
     const int nout = d1 ? 2 : 1;
     const long long npix = (long long)g.nx * g.ny;
+    // Every pass writes the layout buffers: the tag is set again only by a counted pass
+    // that completes (or kept by a pass that reused the layout).
+    const bool had_layout = ws.layout.valid;
+    ws.layout.valid = false;
     if (ws.prof) ASP_TRY(prof_next(ws));
     Plan pl{};
     pl.n = n;
@@ -281,6 +405,26 @@ int project2d_device(Workspace& ws, const Grid& gin, const Src64& s, const float
     ASP_TRY(ensure(ws.items, item_cap(g) * sizeof(Item)));
     ASP_TRY(ensure(ws.iorder, item_cap(g) * sizeof(int)));  // deposit order (k_tilescan)
     ASP_TRY(ensure(ws.merges, merge_cap(g) * sizeof(Merge)));
+    // Layout reuse: caller_arrays -- u, v, h and s are the caller's own device
+    // arrays (or derived from them on every call), not staging copies of host arrays, so
+    // equal addresses mean the same particle set unless the caller rewrote it in place.
+    int reuse = 0;  // stats[15]: 1 the layout was reused, 2 tried and rejected
+    const bool may_reuse = caller_arrays && !xa && !bin_only && reuse_layout_on() &&
+                           speculate_on() && !env_set("ASP_COUNT_EVALS");
+    if (may_reuse && had_layout && ws.layout.armed) {
+        const LayoutKey key = layout_key(ws, g, s, pl, du, dv, dh);
+        if (memcmp(&key, &ws.layout.key, sizeof(key)) == 0) {
+            ASP_TRY(reuse_pass(ws, g, s, pl, kid, nout, det, du, dv, dh, da0, da1, d0, d1, flags,
+                               st, reuse));
+            if (reuse == 1) {
+                ws.layout.valid = true;
+                return ASP_OK;
+            }
+            // a rejected attempt disarms at once: the counted pass below may leave early
+            // (kRetSplit, an error) before it tags the layout
+            if (reuse == 2) ws.layout.armed = false;
+        }
+    }
     ASP_TRY(counters_begin(ws, cNum, st));
     int* dc = (int*)ws.counters.p;
     ASP_TRY(launch_count(g, s, ws, pl, du, dv, dh, st));
@@ -409,21 +553,23 @@ int project2d_device(Workspace& ws, const Grid& gin, const Src64& s, const float
         ws.stats[11] = (long long)e[1];
         ws.stats[12] = (long long)e[2];
     }
-    ws.stats[0] = pl.n_recs;
-    ws.stats[1] = pl.n_items;
-    ws.stats[2] = pl.n_wide;
-    ws.stats[3] = kTile;
-    ws.stats[4] = g.ntiles;
-    ws.stats[5] = hc[cChunk];
-    ws.stats[6] = pl.n_merges;
-    ws.stats[7] = pl.n_slabs;
-    ws.stats[8] = pl.n_large;
     // how this pass's records were scattered: 1 the speculative launch (enqueued before the
     // counter read-back) was kept, 2 placement trials (stats[14] scatter runs), 3 the
     // speculative launch found the buffers too small and the scatter was relaunched after
     // growing them, 0 no earlier buffers (one plain launch)
-    ws.stats[13] = pre ? 1 : placed ? 2 : spec ? 3 : 0;
-    ws.stats[14] = ntrials;
+    pass_stats(ws, g, pl, hc[cChunk], pre ? 1 : placed ? 2 : spec ? 3 : 0, ntrials, reuse);
+    if (!xa) {  // the layout buffers are whole and this pass's: tag them
+        Layout& L = ws.layout;
+        const long long c[kLayoutCounters] = {pl.n_recs, pl.n_items, pl.n_merges, pl.n_slabs,
+                                              pl.n_wide, pl.n_large, hc[cChunk]};
+        if (reuse == 2) L.armed = false;
+        else if (!L.armed) L.armed = L.have_last && std::equal(c, c + 6, L.last);
+        std::copy(c, c + kLayoutCounters, L.ctr);
+        std::copy(c, c + kLayoutCounters, L.last);
+        L.have_last = true;
+        L.key = layout_key(ws, g, s, pl, du, dv, dh);
+        L.valid = caller_arrays;
+    }
     return ASP_OK;
 }
 
@@ -447,11 +593,12 @@ static Src64 src_from(const Src64& s, long long b) {  // particles b.. of s
 // is formed at the end.
 // rows [row_lo, row_hi) of the image only (asp_project2d_rows; default the whole image),
 // d0 / d1 pointing at row row_lo: windows of <= window_rows tile rows from row_lo on.
+// caller_arrays: the particle arrays are the caller's device arrays (project2d_device).
 int project2d_full(Workspace& ws, const Grid& full, const Src64& s, const float* du,
                    const float* dv, const float* dh, const float* da0, const float* da1,
                    long long n, int kid, int flags, float* d0, float* d1, hipStream_t st,
-                   int device, int row_lo = 0, int row_hi = -1, const XArgs* xa = nullptr,
-                   int nxp = 0, float* const* xo = nullptr) {
+                   int device, bool caller_arrays, int row_lo = 0, int row_hi = -1,
+                   const XArgs* xa = nullptr, int nxp = 0, float* const* xo = nullptr) {
     const int wr = window_rows(full);
     long long agg[kNStats] = {0};
     if (row_hi < 0) row_hi = full.gnx;
@@ -474,16 +621,17 @@ int project2d_full(Workspace& ws, const Grid& full, const Src64& s, const float*
             }
             ASP_TRY(project2d_device(ws, g, src_from(s, a), du + a, dv + a, dh + a, da0 + a,
                                      da1 ? da1 + a : nullptr, b - a, kid, f, w0, w1, st, nullptr,
-                                     xa ? &xb : nullptr, nxp, wx));
+                                     xa ? &xb : nullptr, nxp, wx, caller_arrays));
             passes = i + 1;
             for (int k : {0, 1, 2, 6, 7, 8, 9, 10, 11, 12, 14}) agg[k] += ws.stats[k];
             agg[13] = std::max(agg[13], ws.stats[13]);
+            agg[15] = std::max(agg[15], ws.stats[15]);
             return ASP_OK;
         }));
         if (passes > 1 && (flags & ASP_F_RATIO))
             ASP_TRY(ratio_stage(ws, w0, w1, (long long)g.nx * g.ny, st));
     }
-    for (int k : {0, 1, 2, 6, 7, 8, 9, 10, 11, 12, 13, 14}) ws.stats[k] = agg[k];
+    for (int k : {0, 1, 2, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15}) ws.stats[k] = agg[k];
     ws.stats[4] = (long long)((row_hi - row_lo + kTile - 1) / kTile) * full.nty;
     stats_publish(ws, device);
     return ASP_OK;
@@ -659,7 +807,7 @@ static int project2d(const float* u, const float* v, const float* h, long long n
         const Src64 s{nullptr, nullptr, nullptr, nullptr, nullptr, 0, du, dv, dh};
         const XArgs xa = extra_args(xw, p.nxp);
         ASP_TRY(project2d_full(ws, g, s, du, dv, dh, da0, da1, n, m.kid, m.flags, d0, d1, st,
-                               m.device, row_lo, row_hi, p.nxp ? &xa : nullptr, p.nxp, m.xouts));
+                               m.device, dev, row_lo, row_hi, p.nxp ? &xa : nullptr, p.nxp, m.xouts));
         if (!dev) ASP_TRY(host_results(m.out0, m.out1, d0, d1, npix, st));
         return ASP_OK;
     });
@@ -741,7 +889,7 @@ static int project2d_f64(const double* pos, const double* h, long long n, int ax
         const XArgs xa = extra_args(xw, p.nxp);
         ASP_TRY(project2d_full(ws, g, s, f[0], f[1], f[2], fa0, fa1, n, m.kid,
                                (m.flags & ~ASP_F_DEVICE_OUTPUTS) | ASP_F_DEVICE_PTRS, d0, d1, st,
-                               m.device, 0, -1, p.nxp ? &xa : nullptr, p.nxp, m.xouts));
+                               m.device, dev, 0, -1, p.nxp ? &xa : nullptr, p.nxp, m.xouts));
         if (!dev_out) ASP_TRY(host_results(m.out0, m.out1, d0, d1, npix, st));
         return ASP_OK;
     });
@@ -948,6 +1096,7 @@ int asp_release(int32_t device) {
         if (hipSetDevice(d) != hipSuccess) continue;
         if (ws.last_ev) (void)hipEventSynchronize(ws.last_ev);
         free_buffers(ws);
+        ws.layout = Layout{};
         if (ws.h_counters) (void)hipHostFree(ws.h_counters);
         ws.h_counters = nullptr;
         release_pinned(ws);

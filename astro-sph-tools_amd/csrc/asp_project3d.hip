@@ -962,6 +962,7 @@ static int cube_pass(Workspace& ws, const Grid3& g, const float* dx, const float
                      int acc, float* dout, hipStream_t st, long long* agg) {
     long long n_recs = 0;
     int n_items = 0, n_merges = 0, n_slabs = 0;
+    ws.layout.valid = false;  // the cube's binning overwrites the 2-D map's layout buffers
     ASP_TRY(ensure_morton3(ws, g, st));
     // count workgroups (scatter workgroups: half as many), at most 384 (round 6, same process
     // at 10^8: 512 / 384 / 256 / 128 -> cube 13.92-13.96 / 13.86-13.87 / 14.46-14.48 / 17.9 ms:

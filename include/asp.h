@@ -566,7 +566,14 @@ int asp_table_interp(const double *table, int32_t ndim, const int32_t *shape,
  * records were scattered (1 the speculative scatter enqueued before the counter read-back
  * was kept, 2 record-placement trials, 3 the speculative scatter found the buffers too
  * small and was relaunched after growing them, 0 one plain launch; the largest code over
- * the passes), stats[14] scatter runs of the placement trials.  Images of more than 4096
+ * the passes), stats[14] scatter runs of the placement trials, stats[15] layout reuse: 1 the
+ * call reused the previous call's bin layout (same device arrays u, v, h, same grid: no
+ * count pass, no scans; its scatter proved the layout exact for the arrays' present
+ * contents, and stats[13] is 1), 2 it tried and the scatter rejected the layout (the
+ * arrays were rewritten in place: the call then counted as usual), 0 not tried; the
+ * environment variable ASP_REUSE_LAYOUT=0 (read per call) switches reuse off, and so do
+ * ASP_NO_SPECULATE (reuse is a speculative launch) and ASP_COUNT_EVALS (the diagnostic
+ * reads the counted pass's records).  Images of more than 4096
  * tiles and batched calls: the sums over all passes.  After asp_knn_smoothing_lengths
  * (ASP_KNN_COUNT) and asp_nearest (ASP_NEAREST_COUNT) the words describe that call: stats[9]
  * = distances evaluated (asp_nearest: over all queries and sets), the map counters 0; after
