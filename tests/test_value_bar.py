@@ -16,6 +16,15 @@ At the offset windows (value_bar.WINDOWS: zoom maps far from the origin, the sam
 * the edge forms' dead zone taken from the local frames' bound passes, and
   taken from max |corner| for the wide class alone is rejected;
 * every class scaled by 1 + 1e-3 is rejected on ``box``.
+
+At the pass seams (value_bar.STRIPS and the pass / ratio rules, for tests/test_gpu_seams.py)
+
+* the local-frame evaluation reproduces the oracle's neighbour counts on both strips and
+  passes the unchanged bar; the absolute-frame one is rejected on ``strip_offgrid``;
+* every class scaled by 1 + 1e-3 is rejected under the pass rule's widest bar as well;
+* the mixed set evaluated in batches, re-rounded to fp32 between them, passes with the rule;
+* an fp32 quotient passes the ratio rule, whose excluded share stays within its cap;
+* the seam set is what the GPU cases rely on, asserted from the reference alone.
 """
 import numpy as np
 import pytest
@@ -274,3 +283,194 @@ def test_global_peak_bar_accepts_a_wrong_wide_class(oracle):
                                   kernel="indicator")
     with pytest.raises(AssertionError, match="worst err/E"):
         vb.assert_terms_close(bad, ref, E)
+
+
+# ------------------------------------------------- pass seams (value_bar.STRIPS, the rules)
+# What tests/test_gpu_seams.py relies on, shown on the CPU from the references alone: the
+# strip's seam set keeps a correct implementation inside the unchanged bar, the bar still
+# bites there and with the pass rule's extra, and the ratio rule holds for an fp32 quotient.
+STRIP_PASSES, MIXED_PASSES = 6, 4  # the most passes the GPU cases take on either set
+
+
+def _strip_evaluations(oracle, kernel, name):
+    """The local-frame fp32 evaluation of the strip's two maps and the neighbour counts,
+    cropped as the references are."""
+    def make():
+        s = vb.strip_set(oracle, kernel, name)
+        ext = vb.strip_ext(name)
+        (g1,), cnt = vb.eval_f32_local_2d(s, s["a"], kernel, vb.STRIP_SIZE, ext)
+        (g0,), _ = vb.eval_f32_local_2d(s, s["a0"], kernel, vb.STRIP_SIZE, ext)
+        return dict(g0=vb.strip_crop(g0), g1=vb.strip_crop(g1), cnt=vb.strip_crop(cnt))
+    return vb._cached(("strip_evals", kernel, name), make)
+
+
+@pytest.mark.parametrize("kernel", vb.KERNELS)
+@pytest.mark.parametrize("name", vb.STRIP_NAMES)
+def test_strip_local_frame_passes(oracle, kernel, name):
+    ref = vb.strip_reference(oracle, kernel, name)
+    ev = _strip_evaluations(oracle, kernel, name)
+    assert np.array_equal(ev["cnt"], ref["cnt"])
+    w1 = vb.assert_terms_close(ev["g1"], ref["r1"], ref["E1"], ref["by_class1"])
+    w0 = vb.assert_terms_close(ev["g0"], ref["r0"], ref["E0"], ref["by_class0"])
+    assert min(w0, w1) > 0.0
+    print(f"VALUE_BAR cpu local frame {name} {kernel}: worst err/E = {max(w0, w1):.3f}")
+
+
+@pytest.mark.parametrize("kernel", vb.KERNELS)
+def test_strip_absolute_frame_is_rejected(oracle, kernel):
+    """On ``strip_offgrid`` the corners X round to the fp32 lattice near 256 (2^-16 .. 2^-15,
+    1/16 .. 1/32 of a pitch): fl32(u) - fl32(X) is rejected.  (``strip_grid`` cannot show it:
+    every corner k 2^-10 <= 256.5 and every fp32 position is exact.)"""
+    name = "strip_offgrid"
+    s = vb.strip_set(oracle, kernel, name)
+    ref = vb.strip_reference(oracle, kernel, name)
+    g, cnt = vb.eval_f32_2d(s, s["a"], kernel, vb.STRIP_SIZE, vb.strip_ext(name))
+    assert np.array_equal(vb.strip_crop(cnt), ref["cnt"])
+    with pytest.raises(AssertionError, match="worst err/E") as bad:
+        vb.assert_terms_close(vb.strip_crop(g), ref["r1"], ref["E1"], ref["by_class1"])
+    print(f"VALUE_BAR cpu absolute frame {name} {kernel}: rejected, "
+          + str(bad.value).split(" at pixel")[0])
+
+
+@pytest.mark.parametrize("kernel", vb.KERNELS)
+@pytest.mark.parametrize("name", vb.STRIP_NAMES)
+def test_strip_scaled_class_is_rejected(oracle, kernel, name):
+    """Each class scaled by 1 + 1e-3, under the plain bar and under the pass rule's widest
+    (STRIP_PASSES passes, with the fixed-point floor)."""
+    s = vb.strip_set(oracle, kernel, name)
+    ref = vb.strip_reference(oracle, kernel, name)
+    wide = vb.with_passes(ref["E1"], ref["S1"], STRIP_PASSES)
+    assert np.all(wide >= ref["E1"]) and np.any(wide > ref["E1"])
+    for k, cname in enumerate(s["names"]):
+        one = vb.strip_crop(vb.class_map2d(oracle, s, s["a"], kernel, k, vb.STRIP_SIZE,
+                                           vb.strip_ext(name)))
+        bad = ref["r1"] + 1e-3 * one
+        with pytest.raises(AssertionError, match="worst err/E"):
+            vb.assert_terms_close(bad, ref["r1"], ref["E1"], ref["by_class1"])
+        with pytest.raises(AssertionError, match="worst err/E") as rej:
+            vb.assert_terms_close(bad, ref["r1"], wide, ref["by_class1"], floor=ref["F1"])
+        print(f"VALUE_BAR cpu scaled {cname} {name} {kernel} P={STRIP_PASSES}: rejected, "
+              + str(rej.value).split(" at pixel")[0])
+
+
+@pytest.mark.parametrize("kernel", vb.KERNELS)
+def test_mixed_scaled_class_is_rejected_under_the_pass_rule(oracle, kernel):
+    s = vb.mixed_set(oracle, kernel)
+    ref = vb.reference2d(oracle, kernel)
+    wide = vb.with_passes(ref["E1"], ref["S1"], MIXED_PASSES + 1)  # (+ 1: a caller's accumulate)
+    for k, cname in enumerate(s["names"]):
+        bad = ref["r1"] + 1e-3 * vb.class_map2d(oracle, s, s["a"], kernel, k)
+        with pytest.raises(AssertionError, match="worst err/E"):
+            vb.assert_terms_close(bad, ref["r1"], wide, ref["by_class1"], floor=ref["F1"])
+
+
+@pytest.mark.parametrize("kernel", vb.KERNELS)
+def test_pass_rule_is_the_bar_with_extra_ulps(oracle, kernel):
+    """with_passes(E, S, P) is bar2d with extra_ulps = 3 (P - 1): term_bound is linear."""
+    s = vb.mixed_set(oracle, kernel)
+    ref = vb.reference2d(oracle, kernel)
+    assert vb.pass_ulps(1) == 0.0 and vb.pass_ulps(4) == 9.0
+    E, _ = vb.bar2d(oracle, s, s["a"], kernel, extra_ulps=vb.pass_ulps(MIXED_PASSES))
+    np.testing.assert_allclose(vb.with_passes(ref["E1"], ref["S1"], MIXED_PASSES), E, rtol=1e-12)
+    assert np.array_equal(ref["S1"] == 0, ref["E1"] == 0)
+
+
+@pytest.mark.parametrize("kernel", vb.KERNELS)
+def test_mixed_set_in_batches_passes(oracle, kernel):
+    """The mixed set evaluated in MIXED_PASSES array-order batches, the map re-rounded to
+    fp32 after each (what accumulating passes store): inside the pass rule's bar."""
+    s = vb.mixed_set(oracle, kernel)
+    ref = vb.reference2d(oracle, kernel)
+    n = s["h"].size
+    edges = np.linspace(0, n, MIXED_PASSES + 1).astype(int)
+    g = np.zeros(vb.SIZE2D)
+    for a, b in zip(edges[:-1], edges[1:]):
+        part = {k: s[k][a:b] for k in ("u", "v", "h")}
+        gb, _ = vb.eval_f32_2d(part, s["a"][a:b], kernel)
+        g = vb.f32(g + gb)
+    E = vb.with_passes(ref["E1"], ref["S1"], MIXED_PASSES)
+    worst = vb.assert_terms_close(g, ref["r1"], E, ref["by_class1"])
+    assert worst > 0.0
+    print(f"VALUE_BAR cpu {MIXED_PASSES} batches {kernel}: worst err/E = {worst:.3f}")
+
+
+def _quotient_f32(g0, g1):
+    g0, g1 = np.asarray(g0, np.float32), np.asarray(g1, np.float32)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(g1 != 0, g0 / g1, np.float32(0.0)).astype(np.float64)
+
+
+@pytest.mark.parametrize("kernel", vb.KERNELS)
+@pytest.mark.parametrize("name", vb.STRIP_NAMES)
+def test_ratio_rule_strip(oracle, kernel, name):
+    """The fp32 quotient of the fp32-stored local-frame maps passes the ratio rule; the
+    pixels it leaves out are within the cap; a quotient off by 1e-3 is rejected."""
+    ref = vb.strip_reference(oracle, kernel, name)
+    ev = _strip_evaluations(oracle, kernel, name)
+    q = _quotient_f32(ev["g0"], ev["g1"])
+    share = vb.ratio_tail_share(ref["r1"], ref["E1"])
+    assert 0.0 < share <= vb.RATIO_TAIL_SHARE
+    worst = vb.assert_ratio_close(q, ref["r0"], ref["r1"], ref["E0"], ref["E1"])
+    assert worst > 0.0
+    print(f"VALUE_BAR cpu ratio {name} {kernel}: worst err/E = {worst:.3f}, "
+          f"tail share {share:.2%}")
+    wide0, wide1 = (vb.with_passes(ref["E" + k], ref["S" + k], STRIP_PASSES) for k in "01")
+    assert vb.ratio_tail_share(ref["r1"], wide1) <= vb.RATIO_TAIL_SHARE
+    with pytest.raises(AssertionError, match="worst err/E"):
+        vb.assert_ratio_close(q * (1 + 1e-3), ref["r0"], ref["r1"], wide0, wide1)
+    with pytest.raises(AssertionError, match="are not 0"):
+        vb.assert_ratio_close(q + (ref["r1"] == 0), ref["r0"], ref["r1"], ref["E0"], ref["E1"])
+
+
+@pytest.mark.parametrize("kernel", vb.KERNELS)
+def test_ratio_rule_mixed_set(oracle, kernel):
+    """On the 256^2 mixed set (the batched ratio cases): the tail share, with the pass
+    rule's widest bar, and the oracle's own quotient under the rule."""
+    ref = vb.reference2d(oracle, kernel)
+    wide0, wide1 = (vb.with_passes(ref["E" + k], ref["S" + k], MIXED_PASSES) for k in "01")
+    assert vb.ratio_tail_share(ref["r1"], wide1) <= vb.RATIO_TAIL_SHARE
+    q = _quotient_f32(ref["r0"], ref["r1"])
+    vb.assert_ratio_close(q, ref["r0"], ref["r1"], ref["E0"], ref["E1"])
+    with pytest.raises(AssertionError, match="worst err/E"):
+        vb.assert_ratio_close(q * (1 + 1e-3), ref["r0"], ref["r1"], wide0, wide1)
+
+
+@pytest.mark.parametrize("raw", [False, True], ids=["fp32", "raw"])
+@pytest.mark.parametrize("kernel", vb.KERNELS)
+@pytest.mark.parametrize("name", vb.STRIP_NAMES)
+def test_strip_set_is_what_the_gpu_cases_rely_on(oracle, kernel, name, raw):
+    s = vb.strip_set(oracle, kernel, name, raw)
+    ext = vb.strip_ext(name)
+    nx, ny = vb.STRIP_SIZE
+    seam, tile = vb.STRIP_SEAM, 64
+    assert (nx + tile - 1) // tile == 4104 and (ny + tile - 1) // tile == 1 and seam == 4096 * tile
+    psx, psy = (ext[1] - ext[0]) / nx, (ext[3] - ext[2]) / nx
+    assert abs(psx / psy - 1.0) < 1e-12  # square pixels
+    for key in ("u", "v", "h", "a", "a0"):
+        assert np.array_equal(s[key], vb.f32(s[key])) != raw, key
+    peak = s["a"] * vb.w0(oracle, kernel, s["h"])
+    assert 0.49 < peak.min() and peak.max() < 1.51
+    # every class has particles whose pixels lie on both sides of the seam (the fp64 test
+    # on rows seam - 1 and seam, the nearest column)
+    Y = ext[2] + np.arange(ny) * psy
+    dy2 = np.min((s["v"][:, None] - Y[None, :]) ** 2, axis=1)
+    below = (s["u"] - (ext[0] + (seam - 1) * psx)) ** 2 + dy2 < (2 * s["h"]) ** 2
+    above = (s["u"] - (ext[0] + seam * psx)) ** 2 + dy2 < (2 * s["h"]) ** 2
+    for k, cname in enumerate(s["names"]):
+        assert np.count_nonzero(below & above & (s["cls"] == k)) >= 1, cname
+    # the wide class: > STRIP_WIDE_TILES tiles in each window, the other classes never
+    lo = np.floor((s["u"] - 2 * s["h"] - ext[0]) / psx).astype(int) + 1  # first / last row met
+    hi = np.ceil((s["u"] + 2 * s["h"] - ext[0]) / psx).astype(int) - 1
+    assert lo.min() >= vb.STRIP_LO + tile
+    t0 = seam // tile - np.minimum(lo, seam) // tile          # tiles below the seam
+    t1 = np.minimum(hi, nx - 1) // tile + 1 - seam // tile    # tiles from the seam on
+    wide = s["cls"] == s["names"].index(vb.STRIP_WIDE[0])
+    limit = int(vb.STRIP_WIDE_TILES)
+    assert np.count_nonzero(wide & (t0 > limit) & (t1 > limit)) >= 8
+    assert np.all((np.maximum(hi, lo) // tile - lo // tile + 1)[~wide] <= limit)
+    # both windows hold pixels next to the seam
+    ref = vb.strip_reference(oracle, kernel, name, raw)
+    k = seam - vb.STRIP_LO
+    for m in (ref["r0"], ref["r1"], ref["cnt"]):
+        assert m[k - 1].any() and m[k].any()
+    assert ref["cnt"].shape == (nx - vb.STRIP_LO, ny)

@@ -49,6 +49,10 @@ Where the constants come from (none of them from the device's output):
   origin to test exactly that; for the raw-fp64 entry points F64_INPUT_ULPS (derived where
   it is defined) covers the device's own rounding of h and a.
 
+* A call of several pipeline passes (windows, batches) widens the bar by the pass rule
+  (PASS_STORES, ``with_passes``); a ratio map is held to the ratio rule
+  (RATIO_TAIL_SHARE, ``assert_ratio_close``).  Both are derived where they are defined.
+
 ``assert_terms_close(g, r, E)`` asserts g == 0 exactly where r == 0 and |g - r| <= E at
 every pixel; a failure reports the worst err/E, its pixel and the class of particle
 that dominates E there.
@@ -108,6 +112,49 @@ CUBE_SHIFT = (67.25, 12.5, 331.0)  # the cube's offset: EXT3D moved by it (corne
 # 4.79 u, taken as 5.  No coordinate term: the local coordinates are formed from the
 # resident fp64 positions (src_u / src_v) and rounded once, which eps_p already holds.
 F64_INPUT_ULPS = 5.0
+
+# Pass seams: a 2-D map call is a loop of pipeline passes -- WINDOWS of whole
+# tile rows where the image has more than 4096 GPU tiles, particle BATCHES where the array
+# exceeds one pass.  The strip makes the window seam cheap: nty = 1 and ntx = 4104, so
+# window 0 is rows [0, 262144) with exactly 4096 tiles, window 1 the last 512 rows, the seam
+# at row STRIP_SEAM, and every particle lies within a few hundred rows of it.  The pixels
+# are square (equal u and v extents: the v pitch divides by nx); the image is not, so the
+# chunk cull is active as on SIZE2D_NONSQUARE.
+#   strip_grid     corners k 2^-10 <= 256.5, all exact in fp32 (the seam at u = 256.0)
+#   strip_offgrid  neither the corners nor the pitch are fp32-representable
+STRIP_SEAM = 262144
+STRIP_SIZE = (STRIP_SEAM + 512, 16)
+STRIP_WIDE_TILES = "2"  # ASP_WIDE_TILES: the strip's wide class alone meets > 2 tiles
+STRIPS = (("strip_grid", (0.0, STRIP_SIZE[0] * 2.0 ** -10, 0.0, STRIP_SIZE[0] * 2.0 ** -10)),
+          ("strip_offgrid", (-3.3, 253.9157, 0.7, 257.9157)))
+STRIP_NAMES = tuple(w[0] for w in STRIPS)
+# The strip's classes: CLASSES_2D with u within +-384 pitches of the seam and v in [-4, 20)
+# pitches, but the wide class at h = 90 .. 120 pitches within +-40 pitches of the seam:
+# 2h - 40 >= 140 pitches, so each of them reaches three tiles on either side; the clump as
+# CLUMP, sigma = 2 pitches about (STRIP_SEAM, 8).
+STRIP_WIDE = ("h90-120", 90.0, 120.0, 12)
+STRIP_CLASSES = CLASSES_2D[:-1] + (STRIP_WIDE,)
+STRIP_REACH, STRIP_WIDE_REACH = 384.0, 40.0
+# No footprint reaches below row STRIP_SEAM - 384 - 24 (wide: - 40 - 240), so the strip's
+# references keep rows [STRIP_LO, nx) only; strip_crop asserts that the rest is 0.
+STRIP_LO = STRIP_SEAM - 512
+
+# Pass rule.  A call of P passes gets extra_ulps = 3 (P - 1) in term_bound: within a pass a
+# pixel is stored at most three times (by the deposit, by the merge of a split tile, by the
+# wide path; gather_emit and the merges always accumulate), passes after the first add to
+# the fp32 map, and each store rounds a partial sum bounded by sum |a_p| W(0, h_p) over the
+# pixel's included particles -- the sum extra_ulps multiplies.  Nothing of it is measured.
+PASS_STORES = 3.0
+
+# Ratio rule (ratio=True: q = g0 / g1 formed in fp32 from the stored components).  With
+# g = r + d, |d| <= E and w = r0 / r1:
+#   |g0 / g1 - w| = |d0 r1 - r0 d1| / (r1 (r1 + d1)) <= (E0 + |w| E1) / (r1 - E1),
+# plus the division's rounding 2^-24 |q| <= 2^-23 |w|, wherever r1 > 2 E1 (so r1 - E1 >
+# r1 / 2); q == 0 exactly where r1 == 0.  Pixels with 0 < r1 <= 2 E1 see kernel tails only:
+# their quotient has no relative precision and is required to be finite; at most
+# RATIO_TAIL_SHARE of the covered pixels may be of that kind, which is asserted of the
+# reference alone (ratio_tail_share).
+RATIO_TAIL_SHARE = 0.02
 
 SIZE3D = (48, 40, 64)
 EXT3D = (-2.0, 2.0, -2.0, 2.0, -2.0, 2.0)
@@ -189,6 +236,40 @@ def mixed_set(oracle, kernel, window=None, raw=False):
                     names=[c[0] for c in CLASSES_2D + (CLUMP,)])
     key = ("mixed", kernel) if window is None and not raw else ("mixed", kernel, window, raw)
     return _cached(key, make)
+
+
+def strip_ext(name):
+    return dict(STRIPS)[name]
+
+
+def strip_set(oracle, kernel, name, raw=False):
+    """The seam set on the strip ``name`` of STRIPS: STRIP_CLASSES about the seam plus the
+    clump on it.  Keys, amplitudes (equal peaks, T, a0 = fl32(a T)) and ``raw`` as
+    mixed_set; lu, lv are the positions in pixel pitches from the corner, before rounding."""
+    def make():
+        ext = strip_ext(name)
+        psx, psy = (ext[1] - ext[0]) / STRIP_SIZE[0], (ext[3] - ext[2]) / STRIP_SIZE[0]
+        pitch = max(psx, psy)
+        rnd = (lambda t: np.asarray(t, np.float64)) if raw else f32
+        rng = np.random.default_rng(24)
+        lu, lv, h, cls = [], [], [], []
+        for k, (cname, lo, hi, n) in enumerate(STRIP_CLASSES + (CLUMP,)):
+            if k < len(STRIP_CLASSES):
+                reach = STRIP_WIDE_REACH if cname == STRIP_WIDE[0] else STRIP_REACH
+                lu.append(STRIP_SEAM + rng.uniform(-reach, reach, n))
+                lv.append(rng.uniform(-4.0, 20.0, n))
+            else:
+                lu.append(rng.normal(STRIP_SEAM, 2.0, n))
+                lv.append(rng.normal(8.0, 2.0, n))
+            h.append(rng.uniform(lo, hi, n) * pitch)
+            cls.append(np.full(n, k))
+        lu, lv = np.concatenate(lu), np.concatenate(lv)
+        u, v, h = rnd(ext[0] + lu * psx), rnd(ext[2] + lv * psy), rnd(np.concatenate(h))
+        a = rnd(rng.uniform(0.5, 1.5, h.size) / w0(oracle, kernel, h))
+        T = rnd(rng.uniform(1.0, 3.0, h.size))
+        return dict(u=u, v=v, h=h, a=a, T=T, a0=rnd(a * T), cls=np.concatenate(cls), lu=lu, lv=lv,
+                    names=[c[0] for c in STRIP_CLASSES + (CLUMP,)])
+    return _cached(("strip", kernel, name, raw), make)
 
 
 def cube_ext(shift=None):
@@ -307,6 +388,88 @@ def bar3d(oracle, s, kernel, size=SIZE3D, ext=EXT3D, planes=None):
         by_class[name] = oracle.project3d(s["x"][m], s["y"][m], s["z"][m], s["h"][m], e[m], size,
                                           ext, kernel="indicator", planes=planes)
     return sum(by_class.values()), by_class
+
+
+def pass_ulps(passes):
+    """The pass rule's extra_ulps for a call of ``passes`` pipeline passes."""
+    assert passes >= 1
+    return PASS_STORES * (passes - 1)
+
+
+def peak_sum2d(oracle, s, a, kernel, size=SIZE2D, ext=EXT2D, chunk=CHUNK):
+    """S(pixel) = sum |a_p| W(0, h_p) over the pixel's included particles: what one ulp of
+    extra_ulps weighs, E(extra_ulps = x) = E(0) + x 2^-24 S (term_bound is linear in it)."""
+    return oracle.project_scatter(s["u"], s["v"], s["h"], np.abs(a) * w0(oracle, kernel, s["h"]),
+                                  None, size, chunk, *ext, kernel="indicator")[0]
+
+
+def peak_sum3d(oracle, s, kernel, size=SIZE3D, ext=EXT3D):
+    return oracle.project3d(s["x"], s["y"], s["z"], s["h"],
+                            np.abs(s["a"]) * w0(oracle, kernel, s["h"]), size, ext,
+                            kernel="indicator")
+
+
+def with_passes(E, S, passes):
+    """The bar E of one pass widened by the pass rule."""
+    return E + pass_ulps(passes) * U24 * S
+
+
+def strip_crop(full, row_lo=0):
+    """Rows [STRIP_LO, nx) of a strip map whose first row is image row ``row_lo``; the rows
+    before them must be 0 (no footprint of the seam set reaches them)."""
+    full = np.asarray(full)
+    k = STRIP_LO - row_lo
+    assert not full[:k].any(), "pixels below STRIP_LO are not 0"
+    return np.array(full[k:], np.float64)
+
+
+def strip_scatter(oracle, s, a0, a1, kernel, ext):
+    """The oracle's strip maps of (a0[, a1]), cropped (strip_crop)."""
+    o0, o1 = oracle.project_scatter(s["u"], s["v"], s["h"], a0, a1, STRIP_SIZE, CHUNK, *ext,
+                                    kernel=kernel)
+    return strip_crop(o0), None if o1 is None else strip_crop(o1)
+
+
+def strip_bar(oracle, s, a, kernel, ext, extra_ulps=0.0):
+    """bar2d on the strip, cropped: (E, by_class)."""
+    E, by_class = bar2d(oracle, s, a, kernel, STRIP_SIZE, ext, extra_ulps=extra_ulps)
+    return strip_crop(E), {n: strip_crop(m) for n, m in by_class.items()}
+
+
+def ratio_tail_share(r1, E1):
+    """The share of the covered pixels (r1 > 0) the ratio rule only requires to be finite."""
+    covered = np.count_nonzero(r1 > 0)
+    return np.count_nonzero((r1 > 0) & (r1 <= 2.0 * E1)) / max(covered, 1)
+
+
+def assert_ratio_close(q, r0, r1, E0, E1):
+    """The ratio rule (see RATIO_TAIL_SHARE): q == 0 exactly where r1 == 0, |q - r0 / r1| <=
+    (E0 + |w| E1) / (r1 - E1) + 2^-23 |w| where r1 > 2 E1, finite elsewhere, and the
+    reference's own share of such pixels within RATIO_TAIL_SHARE.  Returns the worst
+    err / bar."""
+    q = np.asarray(q, np.float64)
+    assert q.shape == r0.shape == r1.shape == E0.shape == E1.shape
+    assert np.all(r1 >= 0.0), "the ratio rule is stated for non-negative weights"
+    assert np.all(np.isfinite(q)), "non-finite pixels"
+    share = ratio_tail_share(r1, E1)
+    assert share <= RATIO_TAIL_SHARE, f"{share:.2%} of the covered pixels are kernel tails"
+    nz = np.count_nonzero(q[r1 == 0])
+    assert nz == 0, f"{nz} pixels without weight are not 0"
+    ok = r1 > 2.0 * E1
+    w = r0[ok] / r1[ok]
+    bar = (E0[ok] + np.abs(w) * E1[ok]) / (r1[ok] - E1[ok]) + 2.0 ** -23 * np.abs(w)
+    err = np.abs(q[ok] - w)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(err == 0, 0.0, err / bar)
+    if ratio.size == 0:
+        return 0.0
+    k = int(np.argmax(ratio))
+    if ratio[k] > 1.0:
+        pix = tuple(int(i[k]) for i in np.nonzero(ok))
+        raise AssertionError(f"worst err/E = {ratio[k]:.3g} at pixel {pix} (q = {q[ok][k]:.9g}, "
+                             f"r0 / r1 = {w[k]:.9g}, bar = {bar[k]:.3g}); "
+                             f"{np.count_nonzero(ratio > 1.0)} pixels over the ratio bar")
+    return float(ratio[k])
 
 
 def assert_terms_close(g, r, E, by_class=None, floor=0.0):
@@ -557,11 +720,33 @@ def reference2d(oracle, kernel, size=SIZE2D, window=None, raw=False):
         cnt, _ = oracle.project_scatter(s["u"], s["v"], s["h"], np.ones(s["h"].size), None, size,
                                         CHUNK, *ext, kernel="indicator")
         return dict(r0=r0, r1=r1, E0=E0, E1=E1, by_class0=c0, by_class1=c1, cnt=cnt,
+                    S0=peak_sum2d(oracle, s, s["a0"], kernel, size, ext),
+                    S1=peak_sum2d(oracle, s, s["a"], kernel, size, ext),
                     F0=fixed_point_term(oracle, kernel, s["h"], s["a0"]),
                     F1=fixed_point_term(oracle, kernel, s["h"], s["a"]))
     key = ("ref2d", kernel, size) if window is None and not raw else \
         ("ref2d", kernel, size, window, raw)
     return _cached(key, make)
+
+
+def strip_reference(oracle, kernel, name, raw=False):
+    """reference2d for strip_set on the strip ``name``, every map cropped to the rows from
+    STRIP_LO on (strip_crop): r0 / r1, E0 / E1, by_class0 / by_class1, the pass rule's S0 /
+    S1 (peak_sum2d), F0 / F1 and the neighbour counts cnt."""
+    def make():
+        s = strip_set(oracle, kernel, name, raw)
+        ext = strip_ext(name)
+        extra = F64_INPUT_ULPS if raw else 0.0
+        r0, r1 = strip_scatter(oracle, s, s["a0"], s["a"], kernel, ext)
+        E0, c0 = strip_bar(oracle, s, s["a0"], kernel, ext, extra)
+        E1, c1 = strip_bar(oracle, s, s["a"], kernel, ext, extra)
+        cnt, _ = strip_scatter(oracle, s, np.ones(s["h"].size), None, "indicator", ext)
+        return dict(r0=r0, r1=r1, E0=E0, E1=E1, by_class0=c0, by_class1=c1, cnt=cnt,
+                    S0=strip_crop(peak_sum2d(oracle, s, s["a0"], kernel, STRIP_SIZE, ext)),
+                    S1=strip_crop(peak_sum2d(oracle, s, s["a"], kernel, STRIP_SIZE, ext)),
+                    F0=fixed_point_term(oracle, kernel, s["h"], s["a0"]),
+                    F1=fixed_point_term(oracle, kernel, s["h"], s["a"]))
+    return _cached(("strip_ref", kernel, name, raw), make)
 
 
 def reference3d(oracle, kernel, shift=None):
@@ -570,7 +755,7 @@ def reference3d(oracle, kernel, shift=None):
         ext = cube_ext(shift)
         r = oracle.project3d(s["x"], s["y"], s["z"], s["h"], s["a"], SIZE3D, ext, kernel=kernel)
         E, c = bar3d(oracle, s, kernel, ext=ext)
-        return dict(r=r, E=E, by_class=c)
+        return dict(r=r, E=E, by_class=c, S=peak_sum3d(oracle, s, kernel, ext=ext))
     return _cached(("ref3d", kernel) if shift is None else ("ref3d", kernel, tuple(shift)), make)
 
 
