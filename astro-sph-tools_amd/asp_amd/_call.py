@@ -10,6 +10,7 @@ entry point keeps the strictness it always had:
     entry point                             host arrays  device tensors
     ======================================  ===========  ===============
     sightline_columns, nearest_haloes       refuse       refuse
+    halo_profiles, aperture_sums            refuse       refuse
     project2d_f64 (create_image)            cast         refuse
     stage_particles, knn_smoothing_lengths  cast         refuse
     the periodic-box helpers                cast         refuse

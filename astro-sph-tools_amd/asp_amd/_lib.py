@@ -111,6 +111,10 @@ POINT_PROTOTYPES = {
     "asp_sample3d": [_f] * 6 + [_Q, _d, _d, _d, _Q, _I, _I, _f, _f, _I, _V],
     "asp_sample3d_f64": [_d] * 4 + [_Q, _d, _d, _d, _Q, _I, _I, _f, _f, _I, _V],
 }
+# The C-ABI of include/asp_profiles.h (halo-centred profiles and aperture sums).
+PROFILE_PROTOTYPES = {
+    "asp_halo_profiles": [_d, _d, _I, _Q, _d, _d, _Q, _d, _I, _R, _i64, _d, _I, _I, _V],
+}
 
 
 class ASPError(RuntimeError):
@@ -137,7 +141,7 @@ def lib():
         except Exception:
             pass
     L = C.CDLL(LIB_PATH)
-    for name, argtypes in {**PROTOTYPES, **POINT_PROTOTYPES}.items():
+    for name, argtypes in {**PROTOTYPES, **POINT_PROTOTYPES, **PROFILE_PROTOTYPES}.items():
         fn = getattr(L, name, None)  # (absent from an older A/B build, ASP_LIB)
         if fn is not None:
             fn.argtypes, fn.restype = argtypes, RESTYPES.get(name, C.c_int)

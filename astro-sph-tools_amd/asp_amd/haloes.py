@@ -1,4 +1,5 @@
-"""Nearest halo centre of every particle in a periodic box, on the GPU.
+"""Nearest halo centre of every particle in a periodic box, and halo-centred radial profiles
+and aperture sums, on the GPU.
 
 Replaces the numerical core of the reference's second command-line tool
 (_scripts/find_nearest_haloes.py:196-221): per minimum-halo-mass cut,
@@ -7,15 +8,23 @@ cuts go to the device in one call (asp_nearest, csrc/asp_nearest.hip): same arit
 scipy's periodic distance, so the distances are bit-identical; the indices refer to the
 full ``centres`` array (``np.take(halo_ids, index)`` needs no masked copy) and exact ties
 go to the lowest index.
+
+The only use of a distance stored beside an R200 is ``r / R200``: ``halo_profiles`` and
+``aperture_sums`` (asp_halo_profiles, csrc/asp_profiles.hip) give the number of particles and
+the sum of up to four particle properties in every radial bin around every halo, with the same
+periodic arithmetic; haloes may overlap, so a particle counts for every halo it lies in.
 """
 from __future__ import annotations
 
 import numpy as np
 
 from . import _lib
-from ._call import alloc_out, call_flags, dptr, is_device, positions_f64, stream_scope
+from ._call import (alloc_out, call_flags, dev_f64, dptr, host_f64, is_device, positions_f64,
+                    stream_scope)
 
 MAX_SETS = 8
+MAX_PROPS = 4
+MAX_BINS = 64
 
 
 def halo_mass_masks(halo_masses, minimum_log10_halo_masses):
@@ -85,3 +94,106 @@ def nearest_haloes(positions, centres, box_width, masks=None, *, device: int = 0
         dptr(pos), n, dptr(cen), m, _lib.ptr(words, u32), nsets, box_width,
         _lib.ptr(index, _lib._i32), dptr(distance), 0, device, None))
     return index, distance
+
+
+def _profile_edges(edges):
+    e = np.ascontiguousarray(np.asarray(edges.cpu() if hasattr(edges, "is_cuda") else edges),
+                             dtype=np.float64)
+    if e.ndim != 1 or not 2 <= e.size <= MAX_BINS + 1:
+        raise ValueError(f"edges must be a 1-D array of 2 .. {MAX_BINS + 1} values, got shape "
+                         f"{e.shape}")
+    if not np.all(np.isfinite(e)) or e[0] < 0 or not np.all(np.diff(e) > 0):
+        raise ValueError("edges must be finite, >= 0 and strictly ascending")
+    return e
+
+
+def _prop_list(props):
+    """None, one array or a sequence of arrays -> a list (a 2-D array or tensor is its rows)."""
+    if props is None:
+        return []
+    if hasattr(props, "is_cuda") or isinstance(props, np.ndarray) or hasattr(props, "units"):
+        return [props] if props.ndim == 1 else list(props)
+    props = list(props)
+    if props and np.ndim(props[0]) == 0:  # one property given as a plain sequence of numbers
+        return [np.asarray(props, dtype=np.float64)]
+    return props
+
+
+def halo_profiles(positions, centres, radii, edges, box_width, props=None, *, device: int = 0,
+                  stream=None, accumulate=None):
+    """``(count, sums)``: the number of particles and the sums of their properties in every
+    radial bin around every halo, in the periodic box of width ``box_width``.
+
+    ``positions``: (N, 3) float64, any values -- a NumPy (or unyt) host array, returning NumPy
+    arrays, or a float64 torch tensor on the GPU, returning tensors there (``props`` are then
+    tensors on that device too).  ``centres``: (M, 3) float64 with every coordinate in
+    [0, box_width).  ``radii``: (M,) float64, finite and >= 0; bin b of halo j holds the
+    particles with ``(edges[b] radii[j])**2 <= d2 < (edges[b + 1] radii[j])**2``, d2 the squared
+    periodic distance to the centre (each particle's nearest image, once).  ``radii=None``:
+    the edges are lengths.  ``edges``: B + 1 finite, strictly ascending values >= 0,
+    1 <= B <= 64.  ``props``: None, one (N,) float64 array or a sequence of up to 4.
+    ``accumulate``: a ``(count, sums)`` pair of an earlier call to add into (the pieces of a
+    particle set split over readers).  Returns ``count`` (M, B) int64 and ``sums``
+    (len(props), M, B) float64.
+    """
+    on_device = is_device(positions)
+    if not on_device:
+        pos, n, _ = positions_f64(positions, cast=False)
+    plist = _prop_list(props)
+    if len(plist) > MAX_PROPS:
+        raise ValueError(f"at most {MAX_PROPS} props per call, got {len(plist)}")
+    cen = positions_f64(centres.cpu() if hasattr(centres, "is_cuda") else centres, "centres",
+                        cast=False)[0]
+    m = cen.shape[0]
+    rad = None
+    if radii is not None:
+        rad = host_f64(radii.cpu() if hasattr(radii, "is_cuda") else radii, "radii", (m,),
+                       cast=False)
+    e = _profile_edges(edges)
+    nbins, nprops = e.size - 1, len(plist)
+    box_width = float(box_width)
+    if on_device:
+        import torch
+        dev = positions.device
+        with stream_scope(dev, stream) as scope:  # the uploads ordered on the call's stream
+            pos, n, _ = positions_f64(positions, cast=False)
+            dprops = None
+            if nprops:
+                dprops = torch.stack([dev_f64(p, f"props[{k}]", (n,), dev)
+                                      for k, p in enumerate(plist)])
+            dcen = torch.from_numpy(cen).to(dev)
+            drad = None if rad is None else torch.from_numpy(rad).to(dev)
+            dedges = torch.from_numpy(e).to(dev)
+            scope.keep(pos, dprops, dcen, drad, dedges)
+            given = accumulate or (None, None)
+            count = alloc_out((m, nbins), torch.int64, dev, given[0], name="accumulate[0]")
+            sums = alloc_out((nprops, m, nbins), torch.float64, dev, given[1], name="accumulate[1]")
+            _lib.check(_lib.lib().asp_halo_profiles(
+                dptr(pos), dptr(dprops), nprops, n, dptr(dcen), dptr(drad), m, dptr(dedges), nbins,
+                box_width, _lib.ptr(count, _lib._i64), dptr(sums),
+                call_flags(device_ptrs=True, accumulate=accumulate is not None),
+                dev.index or 0, scope.raw))
+        return count, sums
+    hprops = None
+    if nprops:
+        hprops = np.stack([host_f64(p, f"props[{k}]", (n,), cast=False)
+                           for k, p in enumerate(plist)])
+    given = accumulate or (None, None)
+    count = alloc_out((m, nbins), np.int64, None, given[0], zeros=True, name="accumulate[0]")
+    sums = alloc_out((nprops, m, nbins), np.float64, None, given[1], zeros=True,
+                     name="accumulate[1]")
+    if m > 0 and n > 0:
+        _lib.require_gpu(device)
+    _lib.check(_lib.lib().asp_halo_profiles(
+        dptr(pos), dptr(hprops), nprops, n, dptr(cen), dptr(rad), m, dptr(e), nbins, box_width,
+        _lib.ptr(count, _lib._i64), dptr(sums) if nprops else None,
+        call_flags(accumulate=accumulate is not None), device, None))
+    return count, sums
+
+
+def aperture_sums(positions, centres, radii, box_width, props=None, factor=1.0, **kw):
+    """``(count (M,), sums (nprops, M))`` inside ``factor * radii`` of every halo: the one bin
+    ``[0, factor]`` of :func:`halo_profiles` (``radii=None``: inside the length ``factor``)."""
+    count, sums = halo_profiles(positions, centres, radii, [0.0, float(factor)], box_width, props,
+                                **kw)
+    return count[:, 0], sums[:, :, 0]

@@ -90,7 +90,7 @@ enum Stage {
 };
 
 // What the slots of the workspace's buffer arrays hold (Workspace::knn, nearest, match,
-// sample, aux, pairs).
+// sample, profiles, aux, pairs).
 // asp_knn_smoothing_lengths
 enum KnnBuf {
     kKnnPos, kKnnH,            // staged positions and smoothing lengths (host callers)
@@ -145,6 +145,22 @@ enum SampleBuf {
     kSmpSorted3,               // point coordinates in cell order (x, then y, then z)
     kSampleBufCount
 };
+// asp_halo_profiles
+enum ProfilesBuf {
+    kProfPos, kProfProps,          // staged particle batch (host callers)
+    kProfCentres, kProfRadius,     // staged centres and radii
+    kProfEdges,                    // staged bin edges
+    kProfCount, kProfSum,          // staged outputs
+    kProfCheck,                    // centre / radius check word
+    kProfKeys, kProfIndex,         // cell keys and particle indices, in / out
+    kProfSortTmp,                  // radix sort scratch
+    kProfCellStart,                // first particle of every cell
+    kProfSorted,                   // wrapped coordinates, then the properties, in cell order (SoA)
+    kProfCand, kProfItems,         // candidates per halo; items per halo, then their exclusive scan
+    kProfScanTmp,                  // scan scratch
+    kProfCounters,                 // pairs tested (ASP_PROFILE_COUNT)
+    kProfilesBufCount
+};
 // Per-call scratch that several entry points reuse, each with its own meaning for slots
 // 0 .. 4 (a local enum at the top of the user); the last holds a call's few 64-bit
 // counter words (asp_stage_particles' image counts, the ASP_COUNT_EVALS sums).
@@ -159,6 +175,7 @@ struct WorkspaceBufs {
     Buf nearest[kNearestBufCount];
     Buf match[kMatchBufCount];
     Buf sample[kSampleBufCount];
+    Buf profiles[kProfilesBufCount];
     Buf aux[kAuxBufCount];
     Buf in[5], out[2], hist, cmx, tile_total, tile_start, tile_k, items, merges, counters, recs,
         wide, slabs, morton, iorder;
