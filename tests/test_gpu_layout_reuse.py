@@ -18,9 +18,34 @@ process.  Bars:
 
 Sizes: 50 000 Plummer particles (49 count batches, 7 count workgroups, 2 scatter
 workgroups, so the per-workgroup runs the proof compares exist) on 256^2 (16 tiles).
+
+Rewrites in place (the tests from ``test_slack_set_is_binned_as_predicted`` on).  The cache
+can only be wrong when a reuse is ACCEPTED over arrays that no longer hold what was
+counted, so these tests rewrite ``layout_ref.slack_set`` -- the same sizes, every box edge
+0.05 px or more from the pixel lattice, positive amplitudes distinct per particle -- on
+the device between two calls and assert the verdict of the ONE call that follows, with the
+knobs of the layout key pinned (``layout_ref.ENV``).  The predictions are those of
+``tests/layout_ref.py``, the NumPy statement of the per-(scatter workgroup, column) counts
+and the wide count, pinned on the CPU by ``tests/test_layout_ref.py``.
+
+* An accepted rewrite moves particles, smoothing lengths or owners but no count:
+  ``layout_reuse == 1`` at once (equal counts => accepted), the maps are the counted
+  pass's under the bars above, the host counters are the counted pass's, the neighbour
+  counts are the oracle's -- and the maps DIFFER from those before the rewrite, which a
+  result computed from anything cached could not.
+* A rejected rewrite is the smallest change of its kind -- one particle a tile over, two
+  particles across scatter workgroups, one record into the large stream, one particle in
+  or out of the wide list (no column moves: only the wide count stands guard), one
+  particle without a footprint, a wide list past its capacity: ``layout_reuse == 2``, the
+  maps (accumulated ones included) bit-identical to the counted pass's, then a counted
+  call (0) and a reused one (1).
+* The sweep applies 24 single-particle moves and requires the verdict ``layout_ref``
+  computes for each, in both directions.
 """
 import numpy as np
 import pytest
+
+import layout_ref as lr
 
 pytestmark = pytest.mark.gpu
 
@@ -320,3 +345,263 @@ def test_fp64_entry_point(fresh, monkeypatch):
     third = det()
     assert _reuse() == 2
     assert _same(third, _off(monkeypatch, det))
+
+
+# ----------------------------------------------------------------------------------
+# rewrites in place, accepted and rejected (tests/layout_ref.py predicts which)
+# ----------------------------------------------------------------------------------
+@pytest.fixture
+def pinned(fresh, monkeypatch):
+    """The knobs the layout depends on (read per call, held in the layout key)."""
+    for k, v in lr.ENV.items():
+        monkeypatch.setenv(k, v)
+
+
+def _dev(a):
+    import torch
+    return torch.from_numpy(np.array(a)).cuda()
+
+
+def _slack(seed=1):
+    """``slack_set(seed)`` and its device arrays x, y, h, a0, a1."""
+    s = lr.slack_set(seed)
+    return s, [_dev(a) for a in (s.u, s.v, s.h, s.a0, s.a1)]
+
+
+def _rewrite(dev, new):
+    """In place: the tensors keep their addresses."""
+    for t, a in zip(dev, new):
+        t.copy_(_dev(a).to(t.dtype))
+
+
+def _modes(x, y, h, a0, a1):
+    import torch
+    from asp_amd.device import project2d
+    ones = torch.ones_like(h)
+    return {
+        "det1": lambda: project2d(x, y, h, a0, kernel="cubic", deterministic=True, **KW),
+        "det2": lambda: project2d(x, y, h, a0, a1, kernel="cubic", deterministic=True, **KW),
+        "fp64": lambda: project2d(x, y, h, a0, a1, kernel="cubic", **KW),
+        "ratio": lambda: project2d(x, y, h, a0, a1, kernel="cubic", ratio=True, **KW),
+        "indicator": lambda: project2d(x, y, h, ones, kernel="indicator", **KW),
+        "column": lambda: project2d(x, y, h, a0, kernel="cubic_column", deterministic=True, **KW),
+    }
+
+
+def _agree(mode, got, ref):
+    """The module's bars: fp64 sums within 2 ulps, the ratio map within 8, all else exact."""
+    if mode in ("fp64", "ratio"):
+        _close(got[0], ref[0], 8 if mode == "ratio" else 2)
+        _close(got[1], ref[1], 2)
+    else:
+        assert _same(got, ref)
+
+
+def _differ(got, old):
+    """Every map changed: a result made from anything cached would not have."""
+    import torch
+    return all(not torch.equal(g, o) for g, o in zip(got, old) if g is not None)
+
+
+def _counters():
+    from asp_amd.device import stats
+    st = stats(0)
+    return {k: st[k] for k in lr.STAT_KEYS}
+
+
+_oracle_counts = {}
+
+
+def _neighbour_counts(oracle, name):
+    """The oracle's neighbour counts of ``slack_set()`` after rewrite ``name`` (once each)."""
+    if name not in _oracle_counts:
+        u, v, h, _ = lr.mutated(name)
+        _oracle_counts[name] = oracle.project_scatter(u, v, h, np.ones(lr.N), None, (G, G), 64, *EXT,
+                                                      kernel="indicator")[0]
+    return _oracle_counts[name]
+
+
+def test_slack_set_is_binned_as_predicted(pinned, monkeypatch):
+    """The counted pass's host counters are those of ``layout_ref``'s table, and the set has
+    what the rewrites are about: wide particles, a large stream, split tiles."""
+    s, dev = _slack()
+    call = _modes(*dev)["det2"]
+    call()
+    assert _reuse() == 0
+    st = _counters()
+    table, n_wide = lr.layout_counts(s.u, s.v, s.h)
+    assert st["records"] == table.sum() and st["large"] == table[:, 16:].sum(), st
+    assert st["wide"] == n_wide == lr.N_WIDE and st["large"] > 0, st
+    assert st["merges"] > 0 and st["slabs"] > st["merges"], st
+    call()
+    assert _reuse() == 1 and _counters() == st
+
+
+# Every accepted rewrite in every mode, but for the indicator mode those under which a map of
+# unit amplitudes cannot change (layout_ref.UNIT_MAP_UNCHANGED says why, and
+# tests/test_layout_ref.py checks it against the oracle): "differs from before" has nothing
+# to see there.
+_ACCEPTED_CASES = [(name, mode) for name in lr.ACCEPTED
+                   for mode in ("det1", "det2", "fp64", "ratio", "indicator", "column")
+                   if not (mode == "indicator" and name in lr.UNIT_MAP_UNCHANGED)]
+
+
+@pytest.mark.parametrize("name,mode", _ACCEPTED_CASES)
+def test_accepted_after_rewrite(pinned, monkeypatch, oracle, name, mode):
+    s, dev = _slack()
+    call = _modes(*dev)[mode]
+    call()
+    assert _reuse() == 0
+    old = call()
+    assert _reuse() == 1
+    u, v, h, _ = lr.mutated(name)
+    _rewrite(dev[:3], (u, v, h))
+    got = call()
+    assert _reuse() == 1, name  # equal counts => accepted, on the first call after the rewrite
+    st = _counters()
+    ref = _off(monkeypatch, call)
+    assert st == _counters()
+    _agree(mode, got, ref)
+    assert _differ(got, old)
+    if mode == "indicator":
+        assert np.array_equal(got[0].double().cpu().numpy(), _neighbour_counts(oracle, name))
+
+
+@pytest.mark.parametrize("mode", ("det2", "indicator", "accumulate"))
+@pytest.mark.parametrize("name", lr.REJECTED)
+def test_rejected_near_misses(pinned, monkeypatch, name, mode):
+    import torch
+    from asp_amd.device import project2d
+    s, dev = _slack()
+    x, y, h, a0, a1 = dev
+    base0 = torch.rand(G, G, device=x.device)
+    base1 = torch.rand(G, G, device=x.device)
+    call = _modes(*dev)[mode] if mode != "accumulate" else (
+        lambda: project2d(x, y, h, a0, a1, kernel="cubic", deterministic=True, accumulate=True,
+                          out0=base0.clone(), out1=base1.clone(), **KW))
+    _arm(call)
+    before = _counters()
+    u, v, hh, _ = lr.mutated(name)
+    _rewrite(dev[:3], (u, v, hh))
+    got = call()
+    assert _reuse() == 2, name
+    after = _counters()
+    if name == "across_groups":  # nothing coarser than the per-workgroup rows tells
+        assert after == before
+    if name == "many_wide":
+        assert after["wide"] == lr.HEAD + lr.N_WIDE == 2040
+    fourth = call()
+    assert _reuse() == 0  # disarmed: counted
+    fifth = call()
+    assert _reuse() == 1  # equal counters re-armed it
+    ref = _off(monkeypatch, call)  # (accumulate: the bases were added to exactly once)
+    assert _same(got, ref) and _same(fourth, ref) and _same(fifth, ref)
+
+
+def test_accepted_fp64_entry_point(pinned, monkeypatch):
+    """fp64 arrays that fp32 cannot hold, rewritten in place: the fp32 working copies are
+    re-derived on every call, or the maps would be the old ones."""
+    import torch
+    from asp_amd.device import project2d_f64
+    s = lr.slack_set()
+    rng = np.random.default_rng(5)
+
+    def wide64(a):  # off the fp32 lattice by 2^-30 relative
+        return np.asarray(a, dtype=np.float64) * (1.0 + rng.choice([-1.0, 1.0], len(a)) * 2.0 ** -30)
+
+    def arrays(u, v, h):
+        return np.stack((wide64(u), wide64(v), np.zeros(lr.N)), 1), wide64(h)
+
+    p0, h0 = arrays(s.u, s.v, s.h)
+    assert not np.array_equal(p0[:, 0], p0[:, 0].astype(np.float32))
+    pos, hd = _dev(p0), _dev(h0)
+    b0, b1 = _dev(s.a0).double(), _dev(s.a1).double()
+    call = lambda: project2d_f64(pos, hd, b0, b1, kernel="cubic", deterministic=True, **KW)  # noqa: E731
+    call()
+    assert _reuse() == 0
+    old = call()
+    assert _reuse() == 1
+    now = (s.u, s.v, s.h)
+    for name in ("jitter", "swap_in_batch"):
+        u, v, h, _ = lr.mutated(name, base=now)
+        _rewrite((pos, hd), arrays(u, v, h))
+        got = call()
+        assert _reuse() == 1, name
+        assert _same(got, _off(monkeypatch, call)), name
+        assert _differ(got, old), name
+        old, now = got, (u, v, h)
+
+
+def test_accepted_rows_window(pinned, monkeypatch):
+    """A window of image rows has its own key, tile grid and local frames."""
+    from asp_amd.device import project2d
+    rows = (64, 192)
+    s, dev = _slack()
+    x, y, h, a0, a1 = dev
+    call = lambda: project2d(x, y, h, a0, a1, kernel="cubic", deterministic=True, rows=rows, **KW)  # noqa: E731
+    call()
+    assert _reuse() == 0
+    old = call()
+    assert _reuse() == 1
+    u, v, hh, _ = lr.mutated("jitter")
+    _rewrite(dev[:3], (u, v, hh))
+    got = call()
+    assert _reuse() == 1
+    assert _same(got, _off(monkeypatch, call)) and _differ(got, old)
+    _arm(call)
+    u = u.copy()
+    lr.move_one_tile(u, lr.pick_one_tile_over(s, rows))  # a particle whose box lies in the window
+    _rewrite(dev[:1], (u,))
+    got = call()
+    assert _reuse() == 2
+    assert _same(got, _off(monkeypatch, call))
+
+
+def test_accepted_on_two_slots(pinned, monkeypatch):
+    """Two streams, two particle sets: a rewrite of one set is accepted on its slot and
+    leaves the other slot's layout and maps alone."""
+    import torch
+    from asp_amd.device import project2d
+    (sa, A), (sb, B) = _slack(seed=5), _slack(seed=6)
+    kw = dict(kernel="cubic", deterministic=True, **KW)
+    torch.cuda.synchronize()
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+
+    def run(k, dev):
+        with torch.cuda.stream(streams[k]):
+            out = project2d(*dev, **kw)
+            return out, _reuse()
+
+    for want in (0, 1):
+        old_a, ra = run(0, A)
+        old_b, rb = run(1, B)
+        assert (ra, rb) == (want, want)
+    torch.cuda.synchronize()
+    u, v, h, _ = lr.mutated("jitter", seed=5)
+    with torch.cuda.stream(streams[0]):
+        _rewrite(A[:3], (u, v, h))
+    torch.cuda.synchronize()
+    got_a, ra = run(0, A)
+    got_b, rb = run(1, B)
+    again_b, rb2 = run(1, B)
+    torch.cuda.synchronize()
+    assert (ra, rb, rb2) == (1, 1, 1)
+    assert _same(got_b, old_b) and _same(again_b, old_b)
+    assert _differ(got_a, old_a)
+    assert _same(got_a, _off(monkeypatch, lambda: project2d(*A, **kw)))
+
+
+def test_verdict_follows_the_counts(pinned, monkeypatch):
+    """24 single-particle moves, one after another: the verdict is ``layout_ref``'s for every
+    one of them (8 accepted, 16 rejected), the maps the counted pass's."""
+    s, dev = _slack()
+    x, y, h = dev[:3]
+    call = _modes(*dev)["det2"]
+    moves = lr.sweep()
+    assert len(moves) == 24
+    for k, (p, pu, pv, ph, want) in enumerate(moves):
+        _arm(call)
+        x[p], y[p], h[p] = float(pu), float(pv), float(ph)
+        got = call()
+        assert _reuse() == want, (k, p, want)
+        assert _same(got, _off(monkeypatch, call)), (k, p)
