@@ -149,6 +149,61 @@ def call_flags(device_ptrs=False, ratio=False, accumulate=False, deterministic=F
             | (_lib.ASP_F_DEVICE_OUTPUTS if device_outputs else 0))
 
 
+def sample_sums(entry, lead, positions, smoothing_lengths, particle_properties, weights, points,
+                widths, columns, kid, deterministic, device, stream):
+    """What ``sightline_columns`` and ``sample_points`` share: the float64 checks of the
+    particle fields and of ``points`` ((M, w) with w in ``widths``), on the host or on
+    ``positions``' device, the ``A * w`` product for ``weights``, the float32 output(s) and the
+    call of the ``_f64`` entry point ``entry``, whose arguments after N are ``lead``, then the
+    point columns ``columns(w)``.  Returns the (M,) sums, or weighted means with ``weights``."""
+    fields = ((smoothing_lengths, "smoothing_lengths"), (particle_properties, "particle_properties"),
+              (weights, "weights"))
+    shapes = " or ".join(f"(M, {w})" for w in widths)
+
+    def call(on_device, pos, h, a0, a1, n, cols, m, out0, out1, dev_index, raw):
+        _lib.check(getattr(_lib.lib(), entry)(
+            dptr(pos), dptr(h), dptr(a0), dptr(a1), n, *lead, *map(dptr, cols), m, kid,
+            call_flags(on_device, weights is not None, deterministic=deterministic),
+            _lib.ptr(out0), _lib.ptr(out1), dev_index, raw))
+
+    if is_device(positions):
+        import torch
+        dev = positions.device
+        pts = points
+        if (not is_device(pts) or pts.dtype != torch.float64 or pts.device != dev
+                or pts.dim() != 2 or pts.shape[1] not in widths):
+            raise ValueError(f"points must be an {shapes} float64 tensor on {dev}")
+        m = pts.shape[0]
+        with stream_scope(dev, stream) as scope:  # the temporaries are ordered on the call's stream
+            pos, n, _ = positions_f64(positions, cast=False)
+            h, a0, a1 = (None if a is None else dev_f64(a, name, (n,), dev) for a, name in fields)
+            cols = [pts[:, c].contiguous() for c in columns(pts.shape[1])]
+            if a1 is not None:
+                a0 = a0 * a1
+            out0 = alloc_out((m,), torch.float32, dev)
+            out1 = None if a1 is None else alloc_out((m,), torch.float32, dev)
+            scope.keep(pos, h, a0, a1, *cols, out1)
+            call(True, pos, h, a0, a1, n, cols, m, out0, out1, dev.index or 0, scope.raw)
+        return out0
+    pos, n, _ = positions_f64(positions, cast=False)
+    h, a0, a1 = (None if a is None else host_f64(a, name, (n,), cast=False) for a, name in fields)
+    pts = np.asarray(points)
+    if pts.ndim != 2 or pts.shape[1] not in widths:
+        raise ValueError(f"points must have shape {shapes}, got {pts.shape}")
+    pts = host_f64(pts, "points", cast=False)
+    cols = [np.ascontiguousarray(pts[:, c]) for c in columns(pts.shape[1])]
+    m = pts.shape[0]
+    if a1 is not None:
+        a0 = a0 * a1
+    out0 = alloc_out((m,), np.float32, None, zeros=True)
+    out1 = None if a1 is None else alloc_out((m,), np.float32, None, zeros=True)
+    if m == 0:
+        return out0
+    _lib.require_gpu(device)
+    call(False, pos, h, a0, a1, n, cols, m, out0, out1, device, None)
+    return out0
+
+
 def alloc_out(shape, dtype, dev, given=None, *, zeros=False, name="outputs"):
     """A fresh output of ``shape`` -- a tensor of torch ``dtype`` on ``dev``, or a NumPy array
     of NumPy ``dtype`` when ``dev`` is None -- or ``given`` after checking that it is one:

@@ -5,7 +5,8 @@ the corners of a voxel lattice -- at M arbitrary positions: halo centres, star o
 particles, the particles of another snapshot.  :func:`sightline_profiles` places the points
 along sightlines of any direction (the start position and direction vector of
 ``LineOfSightFileBase``, _LineOfSightBase.py:16-73) and returns the run of the field along
-each one.  Both go through asp_sample3d_f64 (include/asp_points.h, csrc/asp_sample3d.hip):
+each one.  Both go through asp_sample3d_f64 (include/asp_points.h; csrc/asp_sample3d.hip and the
+point grid it shares with the 2-D sampler, csrc/asp_sample.hpp):
 the neighbour test ``r2 < (2h)**2`` in fp64 on the reader's own arrays, bit-exact neighbour
 sets, fp32 terms.
 """
@@ -13,9 +14,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import _lib
-from ._call import (alloc_out, call_flags, dev_f64, dptr, host_f64, is_device, positions_f64,
-                    stream_scope)
+from ._call import dev_f64, host_f64, is_device, sample_sums, stream_scope
 from .tools.projections._kernels import COLUMN_KERNEL_IDS, named_kernel_id
 
 __all__ = ["sample_points", "sightline_profiles", "sightline_points"]
@@ -48,50 +47,8 @@ def sample_points(positions, smoothing_lengths, particle_properties, points, ker
     kid = _volume_kernel_id(kernel)
     if deterministic and weights is not None:
         raise ValueError("deterministic sums cannot be combined with weights (a ratio)")
-    fields = ((smoothing_lengths, "smoothing_lengths"), (particle_properties, "particle_properties"),
-              (weights, "weights"))
-    if is_device(positions):
-        import torch
-        dev = positions.device
-        pts = points
-        if (not is_device(pts) or pts.dtype != torch.float64 or pts.device != dev
-                or pts.dim() != 2 or pts.shape[1] != 3):
-            raise ValueError(f"points must be an (M, 3) float64 tensor on {dev}")
-        m = pts.shape[0]
-        with stream_scope(dev, stream) as scope:  # the temporaries are ordered on the call's stream
-            pos, n, _ = positions_f64(positions, cast=False)
-            h, a0, a1 = (None if a is None else dev_f64(a, name, (n,), dev) for a, name in fields)
-            px, py, pz = (pts[:, c].contiguous() for c in range(3))
-            if a1 is not None:
-                a0 = a0 * a1
-            out0 = alloc_out((m,), torch.float32, dev)
-            out1 = None if a1 is None else alloc_out((m,), torch.float32, dev)
-            scope.keep(pos, h, a0, a1, px, py, pz, out1)
-            _lib.check(_lib.lib().asp_sample3d_f64(
-                dptr(pos), dptr(h), dptr(a0), dptr(a1), n, dptr(px), dptr(py), dptr(pz), m, kid,
-                call_flags(True, weights is not None, deterministic=deterministic),
-                _lib.ptr(out0), _lib.ptr(out1), dev.index or 0, scope.raw))
-        return out0
-    pos, n, _ = positions_f64(positions, cast=False)
-    h, a0, a1 = (None if a is None else host_f64(a, name, (n,), cast=False) for a, name in fields)
-    pts = np.asarray(points)
-    if pts.ndim != 2 or pts.shape[1] != 3:
-        raise ValueError(f"points must have shape (M, 3), got {pts.shape}")
-    pts = host_f64(pts, "points", cast=False)
-    px, py, pz = (np.ascontiguousarray(pts[:, c]) for c in range(3))
-    m = pts.shape[0]
-    if a1 is not None:
-        a0 = a0 * a1
-    out0 = alloc_out((m,), np.float32, None, zeros=True)
-    out1 = None if a1 is None else alloc_out((m,), np.float32, None, zeros=True)
-    if m == 0:
-        return out0
-    _lib.require_gpu(device)
-    _lib.check(_lib.lib().asp_sample3d_f64(
-        dptr(pos), dptr(h), dptr(a0), dptr(a1), n, dptr(px), dptr(py), dptr(pz), m, kid,
-        call_flags(False, weights is not None, deterministic=deterministic),
-        _lib.ptr(out0), _lib.ptr(out1), device, None))
-    return out0
+    return sample_sums("asp_sample3d_f64", (), positions, smoothing_lengths, particle_properties,
+                       weights, points, (3,), lambda w: (0, 1, 2), kid, deterministic, device, stream)
 
 
 def sightline_points(starts, directions, lengths, n_bins):

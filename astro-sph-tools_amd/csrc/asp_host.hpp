@@ -128,21 +128,19 @@ enum MatchBuf {
     kMatchRows, kMatchRowsOut, kMatchRowIndex,  // asp_take_rows: staged rows, output, index
     kMatchBufCount
 };
-// asp_sample2d / asp_sample2d_f64
+// asp_sample2d / asp_sample3d and their _f64 forms (sample_driver, asp_sample.hpp)
 enum SampleBuf {
     kSmpPart0, kSmpPart1, kSmpPart2, kSmpPart3, kSmpPart4,  // staged particle arrays (host callers)
-    kSmpPx, kSmpPy,            // staged point coordinates
+    kSmpPx, kSmpPy,            // staged point coordinates (the third: kSmpPz)
     kSmpOut0, kSmpOut1,        // staged outputs
     kSmpDesc,                  // the point grid's descriptor (bounding box, scales, counters)
     kSmpKeys, kSmpIndex,       // cell keys and point indices, in / out
     kSmpSortTmp,               // radix sort scratch
     kSmpCellCount, kSmpCellStart,  // points per cell and their exclusive scan
     kSmpScanTmp,               // scan scratch
-    kSmpSorted,                // point coordinates in cell order (x, then y)
+    kSmpSorted,                // point coordinates in cell order (x, then y, then z in 3-D)
     kSmpAcc,                   // per-point accumulators (fp64 or int64), in cell order
-    // asp_sample3d / asp_sample3d_f64 (the slots above, and:)
-    kSmpPz,                    // staged third point coordinate
-    kSmpSorted3,               // point coordinates in cell order (x, then y, then z)
+    kSmpPz,                    // staged third point coordinate (3-D)
     kSampleBufCount
 };
 // asp_halo_profiles

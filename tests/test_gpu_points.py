@@ -371,6 +371,81 @@ def test_batches_and_device_edges(gpu, oracle, monkeypatch):
     assert np.all(g == 0)
 
 
+# ------------------------------------------- 4b. what the 2-D and the 3-D sampler share
+N_SHARED, M_SHARED_2D, M_SHARED_3D = 4096, 1500, 3000
+
+
+def shared_reference(oracle):
+    """4 096 particles drawn the way the cube set is (default_rng(39): positions uniform in
+    +-2.2, h in the cube set's two narrow classes, a = U(0.5, 1.5) / W(0); the cube set itself
+    has 3 624 and cannot be asked for more), a0 = fl32(a T); 1 500 points for the 2-D call
+    (the x, y columns of particles and points) and 3 000 for the 3-D call, uniform in +-2.6.
+    The references are the two files' brute forces, the bars have pitch = 0 (both samplers
+    form the pair difference in fp64: no frame term)."""
+    def make():
+        rng = np.random.default_rng(39)
+        h = vb.f32(rng.uniform(0.6, 3.0, N_SHARED) * vb.PITCH3D)
+        x, y, z = (vb.f32(rng.uniform(-2.2, 2.2, N_SHARED)) for _ in range(3))
+        a = vb.f32(rng.uniform(0.5, 1.5, N_SHARED) / vb.w0(oracle, "cubic", h))
+        a0 = vb.f32(a * vb.f32(rng.uniform(1.0, 3.0, N_SHARED)))
+        P = rng.uniform(-2.6, 2.6, (M_SHARED_3D, 3))
+        px, py, pz = (np.ascontiguousarray(P[:, d]) for d in range(3))
+        c = dict(x=x, y=y, z=z, h=h, a=a, a0=a0, px=px, py=py, pz=pz)
+        c["r2"], c["E2"], c["cnt2"] = sr.reference(oracle, "cubic", x, y, h, [a0, a], px[:M_SHARED_2D],
+                                                   py[:M_SHARED_2D], pitch=0.0)
+        c["r3"], c["E3"], c["cnt3"] = s3.reference(oracle, "cubic", x, y, z, h, [a0, a], px, py, pz)
+        c["F"] = [sr.fixed_point_term(oracle, "cubic", h, a0), sr.fixed_point_term(oracle, "cubic", h, a)]
+        return c
+    return _cached("shared", make)
+
+
+def sample2d(u, v, h, a0, px, py, kernel, a1, flags):
+    """asp_sample2d on host arrays, two sums; returns (out0, out1) as float64."""
+    from asp_amd import _lib
+    u, v, h, a0, a1 = (_f32(t) for t in (u, v, h, a0, a1))
+    px, py = _f64(px), _f64(py)
+    out0, out1 = _outs(px.size, True, None, None)
+    P, D = _lib.ptr, (lambda t: _lib.ptr(t, _lib._d))
+    _lib.check(_lib.lib().asp_sample2d(P(u), P(v), P(h), P(a0), P(a1), u.size, D(px), D(py), px.size,
+                                       sr.KERNEL_IDS[kernel], flags, P(out0), P(out1), 0, None))
+    return out0.astype(np.float64), out1.astype(np.float64)
+
+
+@pytest.mark.parametrize("batch", [None, "1000"])
+def test_2d_and_3d_calls_share_one_workspace(gpu, oracle, monkeypatch, batch):
+    """asp_sample2d (1 500 points), asp_sample3d (3 000), and both again, in one process, from
+    host fp32 arrays with two sums under ASP_F_DETERMINISTIC: the sorted coordinates of both
+    live in one workspace slot, which grows between the calls, and the particle batches of
+    both are staged through the same slots (coordinates, h, the two amplitudes sharing the
+    last) -- in one batch and in five (ASP_MAX_BATCH=1000).  The repeats are bitwise equal
+    (fixed-point sums do not depend on the order of the adds); every result is under the
+    value bar (E + fixed_point_term) and every neighbour count is the oracle's."""
+    from asp_amd import _lib
+    _knobs(monkeypatch)
+    if batch:
+        monkeypatch.setenv("ASP_MAX_BATCH", batch)
+    c = shared_reference(oracle)
+    det, ones = _lib.ASP_F_DETERMINISTIC, np.ones(N_SHARED)
+    p2 = (c["px"][:M_SHARED_2D], c["py"][:M_SHARED_2D])
+    assert np.count_nonzero(c["cnt2"]) > 1000 and np.count_nonzero(c["cnt3"]) > 1000
+    assert np.count_nonzero(c["cnt3"] == 0) > 100, "points with no neighbour"
+    got = {2: [], 3: []}
+    for _ in range(2):
+        got[2].append(sample2d(c["x"], c["y"], c["h"], c["a0"], *p2, "cubic", c["a"], det))
+        cnt = sample2d(c["x"], c["y"], c["h"], ones, *p2, "indicator", ones, 0)
+        assert np.array_equal(cnt[0], c["cnt2"]) and np.array_equal(cnt[1], c["cnt2"])
+        got[3].append(sample(*xyz(c), c["h"], c["a0"], *pts(c), "cubic", a1=c["a"], flags=det))
+        cnt = sample(*xyz(c), c["h"], ones, *pts(c), "indicator", a1=ones)
+        assert np.array_equal(cnt[0], c["cnt3"]) and np.array_equal(cnt[1], c["cnt3"])
+    for dim in (2, 3):
+        first, again = got[dim]
+        assert np.array_equal(first[0], again[0]) and np.array_equal(first[1], again[1]), dim
+        for g in got[dim]:
+            w = max(vb.assert_terms_close(g[i], c[f"r{dim}"][i], c[f"E{dim}"][i], floor=c["F"][i])
+                    for i in range(2))
+            _report(f"shared {dim}-D batch={batch}", w)
+
+
 # ------------------------------------------------------------------- 5. odd values
 ODD = dict(  # appended to a small ordinary set; (x, y, z, h, a)
     h_zero=(0.1, 0.1, 0.1, 0.0, 1.0), h_nan=(0.2, 0.1, 0.0, np.nan, 1.0),
