@@ -369,7 +369,10 @@ extern "C" int asp_table_interp(const double* table, int32_t ndim, const int32_t
     if (mode < 0 || mode > 2 || order < 0 || order > 1) return fail(ASP_ERR_INVALID, "bad mode / order");
     if (n < 0) return fail(ASP_ERR_INVALID, "n < 0");
     if (n == 0) return ASP_OK;
-    if (!table || !points || !out || (mode && (!a0 || !a1))) return fail(ASP_ERR_INVALID, "NULL array");
+    // ncol == 0 (a 1-D table at a fixed value): there are no point columns and the kernel
+    // reads none, so an (n, 0) array's NULL data pointer is accepted
+    if (!table || (!points && ncol > 0) || !out || (mode && (!a0 || !a1)))
+        return fail(ASP_ERR_INVALID, "NULL array");
     ASP_TRY(set_device(device));
     TabND A{};
     long long st = 1;

@@ -543,7 +543,9 @@ int asp_table_interp3(const double *table, int32_t n0, int32_t n1, int32_t n2,
  * _IonisationTable.py:31-49): table (shape[0], ..., shape[ndim-1]) float64 C-order, axes[d]
  * a device pointer to axis d (a HOST array of ndim pointers; shape is a host array too),
  * 1 <= ndim <= 6.  points: (n, ndim) rows, or (n, ndim - 1) rows with `zvalue` inserted at
- * axis `zaxis`.  order 0: scipy's _evaluate_linear (weights multiplied first, every ndim);
+ * axis `zaxis` (for ndim 1 that is ncol 0: out is n copies of table(zvalue), as the
+ * reference's evaluate_at_redshift returns; `points` is not read and may be NULL, the data
+ * pointer of an (n, 0) array).  order 0: scipy's _evaluate_linear (weights multiplied first, every ndim);
  * order 1: its Cython 2-D fast path (value times w0 times w1), which scipy takes for a
  * writeable native-float64 2-D table.  Bit-identical to scipy 1.15; fill / NaN / mode as
  * asp_table_interp3.
