@@ -50,6 +50,12 @@ def _member_words(masks, m):
     return words
 
 
+def _host_centres(centres):
+    """The (M, 3) float64 centres as a host array, given on the host or as a tensor."""
+    return positions_f64(centres.cpu() if hasattr(centres, "is_cuda") else centres, "centres",
+                         cast=False)[0]
+
+
 def nearest_haloes(positions, centres, box_width, masks=None, *, device: int = 0, stream=None):
     """(index, distance) of the nearest centre of every position in the periodic box of
     width ``box_width``, per mask.
@@ -65,8 +71,7 @@ def nearest_haloes(positions, centres, box_width, masks=None, *, device: int = 0
     on_device = is_device(positions)
     if not on_device:
         pos, n, _ = positions_f64(positions, cast=False)
-    cen = positions_f64(centres.cpu() if hasattr(centres, "is_cuda") else centres, "centres",
-                        cast=False)[0]
+    cen = _host_centres(centres)
     m = cen.shape[0]
     words = None if masks is None else _member_words(list(masks), m)
     nsets = 1 if masks is None else len(masks)
@@ -142,8 +147,7 @@ def halo_profiles(positions, centres, radii, edges, box_width, props=None, *, de
     plist = _prop_list(props)
     if len(plist) > MAX_PROPS:
         raise ValueError(f"at most {MAX_PROPS} props per call, got {len(plist)}")
-    cen = positions_f64(centres.cpu() if hasattr(centres, "is_cuda") else centres, "centres",
-                        cast=False)[0]
+    cen = _host_centres(centres)
     m = cen.shape[0]
     rad = None
     if radii is not None:

@@ -7,6 +7,7 @@
 #pragma once
 
 #include "asp_device.hpp"
+#include "asp_wave.hpp"
 
 namespace asp {
 
@@ -111,21 +112,12 @@ constexpr int kMinItemRecords1 = 256;
 static __device__ __forceinline__ void block_scan_ll(long long* s, int tid) {
     __shared__ long long part[kScanThreads / 64];
     const int lane = tid & 63, w = tid >> 6;
-    long long x = s[tid];
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        long long y = __shfl_up(x, o);
-        if (lane >= o) x += y;
-    }
+    long long x = wave_incl_scan(s[tid], lane);
     if (lane == 63) part[w] = x;
     __syncthreads();
     if (w == 0) {
-        long long q = lane < kScanThreads / 64 ? part[lane] : 0;
-#pragma unroll
-        for (int o = 1; o < kScanThreads / 64; o <<= 1) {
-            long long y = __shfl_up(q, o);
-            if (lane >= o) q += y;
-        }
+        const long long q =
+            wave_incl_scan<kScanThreads / 64>(lane < kScanThreads / 64 ? part[lane] : 0LL, lane);
         if (lane < kScanThreads / 64) part[lane] = q;
     }
     __syncthreads();
@@ -144,6 +136,8 @@ static __device__ __forceinline__ void block_scan_multi(long long (&x)[M], long 
     long long inc[M];
 #pragma unroll
     for (int m = 0; m < M; ++m) {
+        // (written out: through wave_incl_scan() k_tilescan allocates more registers and
+        // loses a wave of occupancy)
         inc[m] = x[m];
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
@@ -156,12 +150,8 @@ static __device__ __forceinline__ void block_scan_multi(long long (&x)[M], long 
     if (w == 0) {
 #pragma unroll
         for (int m = 0; m < M; ++m) {
-            long long q = lane < kScanThreads / 64 ? part[m][lane] : 0;
-#pragma unroll
-            for (int o = 1; o < kScanThreads / 64; o <<= 1) {
-                long long y = __shfl_up(q, o);
-                if (lane >= o) q += y;
-            }
+            const long long q = wave_incl_scan<kScanThreads / 64>(
+                lane < kScanThreads / 64 ? part[m][lane] : 0LL, lane);
             if (lane < kScanThreads / 64) part[m][lane] = q;
         }
     }

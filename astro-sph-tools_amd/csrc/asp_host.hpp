@@ -1,4 +1,4 @@
-// asp_host.hpp -- host runtime shared by the 2-D and 3-D projectors: errors, the
+// asp_host.hpp -- host runtime shared by every unit: errors, environment knobs, the
 // per-device workspace cache (HBM buffers reused across calls), HIP-event stage timing.
 #pragma once
 
@@ -536,6 +536,29 @@ inline int to_host(void* dst, const void* src, size_t bytes, hipStream_t st) {
     ASP_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
     return ASP_OK;
 }
+
+// A one-word diagnostic counter behind an environment switch (ASP_NEAREST_COUNT,
+// ASP_PROFILE_COUNT).  begin(): p is the zeroed word in slot b when the variable is set,
+// null otherwise, and kernels add to a non-null p (an atomic per lane, so off in timed
+// runs); end(): the total goes to asp_last_stats[9].
+struct DiagCounter {
+    unsigned long long* p = nullptr;
+    int begin(const char* env, Buf& b, hipStream_t st) {
+        if (!env_set(env)) return ASP_OK;
+        ASP_TRY(ensure(b, sizeof(*p)));
+        p = (unsigned long long*)b.p;
+        ASP_HIP(hipMemsetAsync(p, 0, sizeof(*p), st));
+        return ASP_OK;
+    }
+    int end(Workspace& ws, hipStream_t st) {
+        if (!p) return ASP_OK;
+        unsigned long long h = 0;
+        ASP_HIP(hipMemcpyAsync(&h, p, sizeof(h), hipMemcpyDeviceToHost, st));
+        ASP_HIP(hipStreamSynchronize(st));
+        ws.stats[9] = (long long)h;
+        return ASP_OK;
+    }
+};
 
 // Dynamic LDS above the 64 KiB default: the kernel's attribute is raised once per (kernel,
 // device) to at least `bytes`, under a lock -- calls may run on several threads (one per

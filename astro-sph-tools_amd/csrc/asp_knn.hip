@@ -32,6 +32,7 @@
 #include "../../include/asp.h"
 #include "asp_host.hpp"
 #include "asp_prims.hpp"
+#include "asp_wave.hpp"
 
 namespace asp {
 
@@ -580,9 +581,7 @@ __device__ __forceinline__ void wave_scan(long long a, long long b, const double
             ly[lane] = ys[c + lane];
             lz[lane] = zs[c + lane];
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
         for (int q = 0; q < m; ++q) {
             double d = dist2(x, y, z, lx[q], ly[q], lz[q]);
             if (d < C.T.mx) C.push(d);
@@ -719,9 +718,7 @@ __device__ __forceinline__ void wave_stream32(long long nent, At at, const doubl
             fz[lane] = 0.0f;
         }
         const double M = fmax(mq, wave_max(me));
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
         const float Mf = (float)M * (1.0f + 0x1p-22f);  // >= M
         auto bound = [&]() -> float {
             if (!part) return -1.0f;
@@ -892,14 +889,6 @@ __device__ __forceinline__ int wave_min_i(int v) {
 __device__ __forceinline__ int wave_max_i(int v) {
     return wave_reduce_i(v, [](int a, int b) { return max(a, b); });
 }
-__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(v, o, 64);
-        if (lane >= o) v += u;
-    }
-    return v;
-}
 
 // The shared cell pass (round 6).  Each lane's cell pass below looks up and scans its own
 // cells, one dependent load chain after another, while the other lanes of the wave, whose
@@ -1067,9 +1056,7 @@ __global__ __launch_bounds__(kKnnBlock, (K == 32 ? 3 : 1)) ASP_KNN_OCC void k_kn
             }
             long long tot = 0;
             if (!ovf && nc > 0 && diag != 4) {
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_sync();
                 // lookups, 64 entries at a time: each entry's index range minus the window,
                 // as the part below it (la entries from j0) and the part above it (from
                 // max(j0, win1)); entry = offset << 47 | la << 31 | j0
@@ -1097,9 +1084,7 @@ __global__ __launch_bounds__(kKnnBlock, (K == 32 ? 3 : 1)) ASP_KNN_OCC void k_kn
                                      ((unsigned long long)min(la, 0xffffLL) << 31) | (unsigned long long)j0;
                     tot = __shfl(incl, 63, 64);
                 }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_sync();
             }
             if (!ovf && tot <= kUMaxEnt && diag != 2 && diag != 4) {
                 const unsigned long long* L = ucl[wv];

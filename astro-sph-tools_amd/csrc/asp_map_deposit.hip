@@ -9,6 +9,7 @@
 #include "asp_host.hpp"
 #include "asp_map.hpp"
 #include "asp_map_device.hpp"
+#include "asp_wave.hpp"
 
 namespace asp {
 
@@ -201,9 +202,7 @@ __device__ __forceinline__ void deferred(const Grid& g, const Src64& s,
                                          int2 kk, const float* xt, const float* yt,
                                          unsigned long long* acc0, unsigned long long* acc1,
                                          int lane) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
     int idx = lane < cnt ? dlist[first + lane] : -1;
     __builtin_amdgcn_wave_barrier();
     if (idx < 0) return;
@@ -584,19 +583,13 @@ struct OrderLds {  // per wave
     unsigned char tab[kPool];  // position -> pool index, [lane][batch]
 };
 
-__device__ __forceinline__ void wave_lds_sync() {  // LDS written by other lanes of the wave
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // key[j]: packed box word of pool record 64 j + lane; the first n records are live.
 // Returns the pool indices this lane takes in batches 0 .. kPoolBatches-1, one byte each
 // (meaningful for positions 64 j + lane < n only).
 __device__ __forceinline__ unsigned order_pool(const unsigned (&key)[kPoolBatches], int n,
                                                OrderLds& w, int lane) {
     if (lane < 16) w.cnt[lane] = 0;
-    wave_lds_sync();
+    wave_sync();
     int bank[kPoolBatches], r[kPoolBatches];  // bank pair; rank among the pool's records of it
     bool big = false;
 #pragma unroll
@@ -605,7 +598,7 @@ __device__ __forceinline__ unsigned order_pool(const unsigned (&key)[kPoolBatche
         r[j] = j * 64 + lane < n ? atomicAdd(&w.cnt[bank[j]], 1) : 0;
         big |= r[j] >= 64;
     }
-    wave_lds_sync();
+    wave_sync();
     const int c = w.cnt[lane & 15];
     {   // lane r: level r starts at T = sum_b min(cnt[b], r) and holds the banks with cnt > r
         int T = 0;
@@ -618,7 +611,7 @@ __device__ __forceinline__ unsigned order_pool(const unsigned (&key)[kPoolBatche
         }
         w.lvl[lane] = (unsigned)T << 16 | m;
     }
-    wave_lds_sync();
+    wave_sync();
     int pos[kPoolBatches];
     if (__ballot(big)) {  // a bank pair with more than 64 records: the same sums per record
 #pragma unroll
@@ -641,11 +634,11 @@ __device__ __forceinline__ unsigned order_pool(const unsigned (&key)[kPoolBatche
     for (int j = 0; j < kPoolBatches; ++j)
         if (j * 64 + lane < n)
             w.tab[(pos[j] & 63) * kPoolBatches + (pos[j] >> 6)] = (unsigned char)(j * 64 + lane);
-    wave_lds_sync();
+    wave_sync();
     unsigned idx = 0u;
 #pragma unroll
     for (int j = 0; j < kPoolBatches; ++j) idx |= (unsigned)w.tab[lane * kPoolBatches + j] << (8 * j);
-    wave_lds_sync();
+    wave_sync();
     return idx;
 }
 

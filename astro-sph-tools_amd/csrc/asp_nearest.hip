@@ -37,6 +37,7 @@
 
 #include "../../include/asp.h"
 #include "asp_host.hpp"
+#include "asp_periodic.hpp"
 #include "asp_prims.hpp"
 
 namespace asp {
@@ -69,40 +70,6 @@ struct NTab {
     double L, halfL;
 };
 
-// scipy's wrap of a query coordinate into the box: x - floor(x / L) * L, then its two
-// corrections for the rounding of that expression.
-__device__ __forceinline__ double wrap_box(double x, double L) {
-    double w = x - floor(x / L) * L;
-    if (w >= L) w = w - L;
-    if (w < 0.0) w = w + L;
-    return w;
-}
-
-// Cell of a coordinate in [0, L] (a wrapped query may equal L): min(G - 1, floor(c G / L)).
-// The same expression for centres and queries, monotone in c.  Clamped at both ends in
-// fp64: a finite query so large that its wrap loses the box (|x| >~ 2^52 L) still gets a
-// cell inside the table.
-__device__ __forceinline__ int cell_of(double c, int G, double L) {
-    double f = floor(c * (double)G / L);
-    if (!(f >= 0.0)) f = 0.0;
-    if (f > (double)(G - 1)) f = (double)(G - 1);
-    return (int)f;
-}
-
-// scipy's periodic squared distance (wrapped query first): per axis d = w - c folded into
-// [-L/2, L/2], then ((dx dx + dy dy) + dz dz).
-__device__ __forceinline__ double fold(double d, double L, double halfL) {
-    if (d < -halfL) return L + d;
-    if (d > halfL) return d - L;
-    return d;
-}
-__device__ __forceinline__ double pdist2(double wx, double wy, double wz, double cx, double cy,
-                                         double cz, double L, double halfL) {
-    const double dx = fold(wx - cx, L, halfL), dy = fold(wy - cy, L, halfL),
-                 dz = fold(wz - cz, L, halfL);
-    return (dx * dx + dy * dy) + dz * dz;
-}
-
 // Lexicographic (d2, original index): ties in d2 go to the lowest index, whatever the order
 // the entries are met in (the counting sort's order within a cell is not deterministic).
 __device__ __forceinline__ void take(double d2, int idx, double& best, int& bi) {
@@ -112,8 +79,7 @@ __device__ __forceinline__ void take(double d2, int idx, double& best, int& bi) 
     }
 }
 
-// bit 0: a coordinate >= L, bit 1: a negative coordinate, bit 2: a non-finite one;
-// cnt[1 + s] += the members of set s.
+// cnt[0] |= the centre_bits() of every centre; cnt[1 + s] += the members of set s.
 __global__ __launch_bounds__(kNBlock) void k_ncheck(const double* __restrict__ c, long long m,
                                                      const unsigned* __restrict__ member,
                                                      int nsets, double L, int* __restrict__ cnt) {
@@ -121,13 +87,7 @@ __global__ __launch_bounds__(kNBlock) void k_ncheck(const double* __restrict__ c
     int bad = 0;
     unsigned bits = 0;
     if (j < m) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const double v = c[3 * j + a];
-            if (!__builtin_isfinite(v)) bad |= 4;
-            else if (v >= L) bad |= 1;
-            else if (v < 0.0) bad |= 2;
-        }
+        bad = centre_bits(c, j, L);
         bits = member ? member[j] : 1u;
     }
     if (bad) atomicOr(&cnt[0], bad);
@@ -215,7 +175,7 @@ __global__ __launch_bounds__(kNBlock) void k_nkeys(const double* __restrict__ po
 // few ulp -- the other way round the box is no shorter while 2r + 1 <= G (it crosses at
 // least G - |o| - 1 >= |o| cells, and g(o) <= |o| h) -- and the folded difference the
 // distance is built from equals that separation up to one more rounding.  Every bound below
-// is reduced by eps = 2^-20 h >= 2^-28 L (G <= 256), far more than the rounding, so
+// is reduced by eps = face_margin(h), far more than the rounding (asp_periodic.hpp), so
 // "bound^2 > best" proves that the COMPUTED d2 of every centre concerned exceeds best.
 //
 // Pruning (prune != 0, shells with 2r + 1 <= G only): a cell is skipped when the sum over the
@@ -234,7 +194,7 @@ __device__ __forceinline__ void nearest_walk(const NSet S, double L, double half
                                              const int* __restrict__ start, int prune, double& best,
                                              int& bi, unsigned& evals) {
     const int G = S.G;
-    const double h = S.h, eps = h * 0x1p-20;
+    const double h = S.h, eps = face_margin(h);
     const int qx = cell_of(wx, G, L), qy = cell_of(wy, G, L), qz = cell_of(wz, G, L);
     const double flx = wx - (double)qx * h, fux = (double)(qx + 1) * h - wx;
     const double fly = wy - (double)qy * h, fuy = (double)(qy + 1) * h - wy;
@@ -383,13 +343,7 @@ static int nearest(const double* pos, long long n, const double* centres, long l
             ASP_HIP(hipMemcpyAsync(h, dcnt, sizeof(h), hipMemcpyDeviceToHost, st));
             ASP_HIP(hipStreamSynchronize(st));
         }
-        if (h[0] & 4)
-            return fail(ASP_ERR_INVALID, "a centre coordinate is not finite (centres must lie inside "
-                                         "the periodic box [0, box_width))");
-        if (h[0] & 1)
-            return fail(ASP_ERR_INVALID, "a centre coordinate is >= box_width: outside the periodic box");
-        if (h[0] & 2)
-            return fail(ASP_ERR_INVALID, "a centre coordinate is negative: outside the periodic box");
+        ASP_TRY(centre_error(h[0]));
         const int small = (int)env_int("ASP_NEAREST_SMALL", kSmallSet, 0, 1 << 20);  // (tests raise it)
         NTab T;
         T.L = L;
@@ -436,12 +390,9 @@ static int nearest(const double* pos, long long n, const double* centres, long l
         // ---- search, in batches of queries ----
         // ASP_NEAREST_COUNT: count the distances evaluated (one atomic per lane, so off in timed
         // runs) -> asp_last_stats[9]
-        unsigned long long* evc = nullptr;
-        if (env_set("ASP_NEAREST_COUNT")) {
-            ASP_TRY(ensure(ws.nearest[kNearCounter], sizeof(unsigned long long)));
-            evc = (unsigned long long*)ws.nearest[kNearCounter].p;
-            ASP_HIP(hipMemsetAsync(evc, 0, sizeof(unsigned long long), st));
-        }
+        DiagCounter evals;
+        ASP_TRY(evals.begin("ASP_NEAREST_COUNT", ws.nearest[kNearCounter], st));
+        unsigned long long* const evc = evals.p;
         // ASP_NEAREST_SORT (read per call, so one process can time both): 1 = the queries of a
         // batch are searched in the order of their cell key, 0 = in the caller's order
         const bool sorted = env_int("ASP_NEAREST_SORT", kSortQueries) != 0;
@@ -506,12 +457,7 @@ static int nearest(const double* pos, long long n, const double* centres, long l
                                     (size_t)nb * sizeof(double), st));
                 }
         }
-        if (evc) {
-            unsigned long long e = 0;
-            ASP_HIP(hipMemcpyAsync(&e, evc, sizeof(e), hipMemcpyDeviceToHost, st));
-            ASP_HIP(hipStreamSynchronize(st));
-            ws.stats[9] = (long long)e;
-        }
+        ASP_TRY(evals.end(ws, st));
         if (!dev) ASP_HIP(hipStreamSynchronize(st));
         stats_publish(ws, device);
         return ASP_OK;

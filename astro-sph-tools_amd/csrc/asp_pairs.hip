@@ -13,6 +13,7 @@
 #include "asp_host.hpp"
 #include "asp_map.hpp"
 #include "asp_map_device.hpp"
+#include "asp_wave.hpp"
 
 namespace asp {
 
@@ -58,12 +59,7 @@ __global__ __launch_bounds__(kPairsBlock) void k_pairs(
             loc[k] = run;
             run += c[k];
         }
-        long long x = run;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            long long y = __shfl_up(x, o);
-            if (lane >= o) x += y;
-        }
+        const long long x = wave_incl_scan(run, lane);
         if (lane == 63) wsum[wv] = x;
         __syncthreads();
         long long base = tile_base[blockIdx.x] + x - run;

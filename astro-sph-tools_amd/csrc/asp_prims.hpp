@@ -1,6 +1,7 @@
 // asp_prims.hpp -- the two rocprim device primitives the library uses, each behind one
 // function that asks rocprim for its scratch size, grows the workspace slot given for it
-// and runs.  Included by asp_knn.hip, asp_nearest.hip and asp_match.hip only: rocprim's
+// and runs.  Included only by the units that sort or scan (asp_knn.hip, asp_nearest.hip,
+// asp_match.hip, asp_profiles.hip and, through asp_sample.hpp, the two samplers): rocprim's
 // headers are slow to compile.  Both are templates, so a unit instantiates the kernels of
 // the one it calls and no others.
 #pragma once

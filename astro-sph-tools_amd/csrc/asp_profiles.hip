@@ -38,7 +38,9 @@
 
 #include "../../include/asp_profiles.h"
 #include "asp_host.hpp"
+#include "asp_periodic.hpp"
 #include "asp_prims.hpp"
+#include "asp_wave.hpp"
 
 namespace asp {
 namespace {
@@ -71,38 +73,9 @@ struct Span {
     int s0, n0, s1, n1;
 };
 
-// asp_nearest's wrap, cell and distance expressions (asp_nearest.hip has the comments).
-__device__ __forceinline__ double wrap_box(double x, double L) {
-    double w = x - floor(x / L) * L;
-    if (w >= L) w = w - L;
-    if (w < 0.0) w = w + L;
-    return w;
-}
-__device__ __forceinline__ int cell_of(double c, int G, double L) {
-    double f = floor(c * (double)G / L);
-    if (!(f >= 0.0)) f = 0.0;
-    if (f > (double)(G - 1)) f = (double)(G - 1);
-    return (int)f;
-}
-__device__ __forceinline__ double fold(double d, double L, double halfL) {
-    if (d < -halfL) return L + d;
-    if (d > halfL) return d - L;
-    return d;
-}
-__device__ __forceinline__ double pdist2(double wx, double wy, double wz, double cx, double cy,
-                                         double cz, double L, double halfL) {
-    const double dx = fold(wx - cx, L, halfL), dy = fold(wy - cy, L, halfL),
-                 dz = fold(wz - cz, L, halfL);
-    return (dx * dx + dy * dy) + dz * dz;
-}
 __device__ __forceinline__ int modg(int v, int G) {
     v %= G;
     return v < 0 ? v + G : v;
-}
-__device__ __forceinline__ void wave_sync() {  // LDS written by the wave's lanes, read by others
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // The cells of one axis that can hold a member of a halo at c with reach R (>= 0, may be
@@ -112,11 +85,11 @@ __device__ __forceinline__ void wave_sync() {  // LDS written by the wave's lane
 // (~2^-50 L), and the image's cell index is floor(u G / L), the particle's own cell modulo G
 // (a wrapped coordinate equal to L sits in cell G - 1, the upper face of the box: a box
 // that reaches it from either side includes that cell).  The box is widened by
-// margin = 2^-20 h >= 2^-28 L (G <= 256), far more than those roundings and the rounding of
-// c -+ R, so the cell set is a superset.  A reach of L or more (or a non-finite one) takes
-// every cell.
+// face_margin(h), far more than those roundings and the rounding of c -+ R
+// (asp_periodic.hpp), so the cell set is a superset.  A reach of L or more (or a non-finite
+// one) takes every cell.
 __device__ __forceinline__ void axis_range(double c, double R, const PGrid& g, int& lo, int& w) {
-    const double reach = R + g.h * 0x1p-20;
+    const double reach = R + face_margin(g.h);
     lo = 0;
     w = g.G;
     if (!(reach < g.L)) return;
@@ -143,12 +116,12 @@ __device__ __forceinline__ HBox halo_box(const double* __restrict__ centres, lon
 // max(0, gap - eps)^2 of the centre to cell lo + k of an axis, or 0 where no bound holds.
 // The bound needs the folded difference to be the direct one: a box of w < G cells with
 // w h <= L / 2 holds the centre and the cell, so |u - c| <= L / 2 for every image u in the
-// cell and the fold leaves it alone.  eps = 2^-20 h covers the cell faces' and the
-// difference's roundings (as in asp_nearest's walk).
+// cell and the fold leaves it alone.  eps = face_margin(h) covers the cell faces' and the
+// difference's roundings (asp_periodic.hpp).
 __device__ __forceinline__ double gap2(double c, int lo, int w, int k, const PGrid& g) {
     if (w >= g.G || (double)w * g.h > g.halfL) return 0.0;
     const double f0 = (double)(lo + k) * g.h, f1 = (double)(lo + k + 1) * g.h;
-    const double gap = fmax(f0 - c, c - f1) - g.h * 0x1p-20;
+    const double gap = fmax(f0 - c, c - f1) - face_margin(g.h);
     return gap > 0.0 ? gap * gap : 0.0;
 }
 
@@ -180,21 +153,13 @@ __device__ __forceinline__ Span row_span(const HBox& b, const PGrid& g, const in
     return s;
 }
 
-// bit 0: a centre coordinate >= L, 1: negative, 2: non-finite, 3: a negative radius,
-// 4: a non-finite radius.
+// word |= the centre_bits() of every centre; bit 3: a negative radius, 4: a non-finite one.
 __global__ __launch_bounds__(kPBlock) void k_pcheck(const double* __restrict__ c,
                                                      const double* __restrict__ radius, long long m,
                                                      double L, int* __restrict__ word) {
     const long long j = (long long)blockIdx.x * kPBlock + threadIdx.x;
     if (j >= m) return;
-    int bad = 0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double v = c[3 * j + a];
-        if (!__builtin_isfinite(v)) bad |= 4;
-        else if (v >= L) bad |= 1;
-        else if (v < 0.0) bad |= 2;
-    }
+    int bad = centre_bits(c, j, L);
     if (radius) {
         const double r = radius[j];
         if (!__builtin_isfinite(r)) bad |= 16;
@@ -394,6 +359,8 @@ __global__ __launch_bounds__(kPBlock) void k_walk_wave(const Walk W) {
             Span s = {0, 0, 0, 0};
             if (r < nrows) s = row_span(b, W.g, W.start, r, Tout);
             const int first = (lane & 1) ? s.s1 : s.s0, len = (lane & 1) ? s.n1 : s.n0;
+            // (written out: wave_incl_scan() here changes the kernel's register assignment,
+            // and that form was not timed -- DESIGN.md §23)
             int incl = len;
             for (int o = 1; o < 64; o <<= 1) {
                 const int v = __shfl_up(incl, o);
@@ -522,13 +489,7 @@ int profiles(const double* pos, const double* props, int nprops, long long n, co
             ASP_HIP(hipMemcpyAsync(&bad, word, sizeof(int), hipMemcpyDeviceToHost, st));
             ASP_HIP(hipStreamSynchronize(st));
         }
-        if (bad & 4)
-            return fail(ASP_ERR_INVALID, "a centre coordinate is not finite (centres must lie inside "
-                                         "the periodic box [0, box_width))");
-        if (bad & 1)
-            return fail(ASP_ERR_INVALID, "a centre coordinate is >= box_width: outside the periodic box");
-        if (bad & 2)
-            return fail(ASP_ERR_INVALID, "a centre coordinate is negative: outside the periodic box");
+        ASP_TRY(centre_error(bad));
         if (bad & 16) return fail(ASP_ERR_INVALID, "a radius is not finite");
         if (bad & 8) return fail(ASP_ERR_INVALID, "a radius is negative");
 
@@ -559,12 +520,9 @@ int profiles(const double* pos, const double* props, int nprops, long long n, co
         const int prune = env_int("ASP_PROFILE_PRUNE", 1) != 0;
         const int gforce = (int)env_int("ASP_PROFILE_CELLS", 0, 0, kPMaxG);
         const int max_items = (int)std::max(1LL, std::min((long long)kPMaxItems, 0x7fffffffLL / (m + 1)));
-        unsigned long long* ctr = nullptr;
-        if (env_set("ASP_PROFILE_COUNT")) {
-            ASP_TRY(ensure(B[kProfCounters], sizeof(unsigned long long)));
-            ctr = (unsigned long long*)B[kProfCounters].p;
-            ASP_HIP(hipMemsetAsync(ctr, 0, sizeof(unsigned long long), st));
-        }
+        DiagCounter tested;
+        ASP_TRY(tested.begin("ASP_PROFILE_COUNT", B[kProfCounters], st));
+        unsigned long long* const ctr = tested.p;
 
         // ---- the batches ----
         ASP_TRY(ensure(B[kProfCand], (size_t)(m + 1) * sizeof(int)));
@@ -668,12 +626,7 @@ int profiles(const double* pos, const double* props, int nprops, long long n, co
             ASP_TRY(to_host(count, dcount, nacc * sizeof(long long), st));
             if (nprops) ASP_TRY(to_host(sum, dsum, nacc * nprops * sizeof(double), st));
         }
-        if (ctr) {
-            unsigned long long h = 0;
-            ASP_HIP(hipMemcpyAsync(&h, ctr, sizeof(h), hipMemcpyDeviceToHost, st));
-            ASP_HIP(hipStreamSynchronize(st));
-            ws.stats[9] = (long long)h;
-        }
+        ASP_TRY(tested.end(ws, st));
         if (!dev) ASP_HIP(hipStreamSynchronize(st));
         stats_publish(ws, device);
         return ASP_OK;

@@ -333,12 +333,7 @@ __global__ __launch_bounds__(TB) void k3_scatter(
         }
         // the box's six absolute bounds are dealt unpacked (any cube edge: a 16-bit packing
         // overflowed the sign bit from voxel 32768 on)
-        int incl = nbr;  // inclusive scan of the pair counts over the wave
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int v = __shfl_up(incl, d);
-            if (lane >= d) incl += v;
-        }
+        const int incl = wave_incl_scan(nbr, lane);  // of the pair counts over the wave
         const int total = __shfl(incl, 63), excl = incl - nbr;
         for (int r = 0; r < total; r += 64) {
             const int p = r + lane;

@@ -108,7 +108,10 @@ __global__ __launch_bounds__(kSBlock) void k_sample3(const Part<3> P, long long 
                 a = start[base + z0];
                 len = start[base + z1 + 1] - a;
             }
-            int inc = len;  // inclusive scan of the lengths over the wave
+            // inclusive scan of the lengths over the wave (written out: wave_incl_scan() here
+            // changes the kernel's register assignment, and that form was not timed --
+            // DESIGN.md §23)
+            int inc = len;
             for (int o = 1; o < 64; o <<= 1) {
                 const int t = __shfl_up(inc, o);
                 if (lane >= o) inc += t;

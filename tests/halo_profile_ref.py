@@ -7,7 +7,7 @@ d2 = (dx dx + dy dy) + dz dz, T_b = (edges[b] * radius[j])**2; the particle is i
 """
 import numpy as np
 
-from test_nearest_host import wrap
+from periodic_ref import wrap
 
 
 class Ref:

@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 from scipy.spatial import KDTree
 
-from test_nearest_host import bits, brute_nearest, restated_d2, wrap
+from periodic_ref import bits, brute_nearest, restated_d2, wrap
 
 
 def scipy_nearest(q, c, L, mask=None):

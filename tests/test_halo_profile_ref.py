@@ -5,7 +5,7 @@ import numpy as np
 from scipy.spatial import KDTree
 
 from halo_profile_ref import brute_profiles, lattice_case, lattice_shells, mixed_case
-from test_nearest_host import wrap
+from periodic_ref import wrap
 
 
 def test_cumulative_counts_are_scipys_ball_counts():
