@@ -11,5 +11,6 @@ from ._axes import CoordinateAxes  # noqa: F401
 from . import tools  # noqa: F401
 from .sightlines import sightline_columns  # noqa: F401
 from .points import sample_points, sightline_profiles  # noqa: F401
+from .spectra import los_coordinate, sightline_spectra  # noqa: F401
 
 __version__ = "0.1.0"

@@ -10,6 +10,7 @@ entry point keeps the strictness it always had:
     entry point                             host arrays  device tensors
     ======================================  ===========  ===============
     sightline_columns, nearest_haloes       refuse       refuse
+    sightline_spectra                       refuse       refuse
     halo_profiles, aperture_sums            refuse       refuse
     project2d_f64 (create_image)            cast         refuse
     stage_particles, knn_smoothing_lengths  cast         refuse
@@ -150,19 +151,27 @@ def call_flags(device_ptrs=False, ratio=False, accumulate=False, deterministic=F
 
 
 def sample_sums(entry, lead, positions, smoothing_lengths, particle_properties, weights, points,
-                widths, columns, kid, deterministic, device, stream):
-    """What ``sightline_columns`` and ``sample_points`` share: the float64 checks of the
-    particle fields and of ``points`` ((M, w) with w in ``widths``), on the host or on
+                widths, columns, kid, deterministic, device, stream, *, extra=(), bins=(),
+                width=None):
+    """What ``sightline_columns``, ``sample_points`` and ``sightline_spectra`` share: the
+    float64 checks of the particle fields and of ``points`` ((M, w) with w in ``widths``), on
+    the host or on
     ``positions``' device, the ``A * w`` product for ``weights``, the float32 output(s) and the
     call of the ``_f64`` entry point ``entry``, whose arguments after N are ``lead``, then the
-    point columns ``columns(w)``.  Returns the (M,) sums, or weighted means with ``weights``."""
+    point columns ``columns(w)``.  Returns the (M,) sums, or weighted means with ``weights``.
+
+    ``sightline_spectra`` adds ``extra``, further (N,) particle fields as (array, name) that the
+    entry point takes before N, ``bins``, its scalars between M and the kernel id, and
+    ``width``, the values per point: the result is (M, width)."""
     fields = ((smoothing_lengths, "smoothing_lengths"), (particle_properties, "particle_properties"),
               (weights, "weights"))
+    shape = (lambda m: (m,)) if width is None else (lambda m: (m, width))
     shapes = " or ".join(f"(M, {w})" for w in widths)
 
-    def call(on_device, pos, h, a0, a1, n, cols, m, out0, out1, dev_index, raw):
+    def call(on_device, pos, h, a0, a1, more, n, cols, m, out0, out1, dev_index, raw):
         _lib.check(getattr(_lib.lib(), entry)(
-            dptr(pos), dptr(h), dptr(a0), dptr(a1), n, *lead, *map(dptr, cols), m, kid,
+            dptr(pos), dptr(h), dptr(a0), dptr(a1), *map(dptr, more), n, *lead, *map(dptr, cols), m,
+            *bins, kid,
             call_flags(on_device, weights is not None, deterministic=deterministic),
             _lib.ptr(out0), _lib.ptr(out1), dev_index, raw))
 
@@ -177,16 +186,18 @@ def sample_sums(entry, lead, positions, smoothing_lengths, particle_properties, 
         with stream_scope(dev, stream) as scope:  # the temporaries are ordered on the call's stream
             pos, n, _ = positions_f64(positions, cast=False)
             h, a0, a1 = (None if a is None else dev_f64(a, name, (n,), dev) for a, name in fields)
+            more = [dev_f64(a, name, (n,), dev) for a, name in extra]
             cols = [pts[:, c].contiguous() for c in columns(pts.shape[1])]
             if a1 is not None:
                 a0 = a0 * a1
-            out0 = alloc_out((m,), torch.float32, dev)
-            out1 = None if a1 is None else alloc_out((m,), torch.float32, dev)
-            scope.keep(pos, h, a0, a1, *cols, out1)
-            call(True, pos, h, a0, a1, n, cols, m, out0, out1, dev.index or 0, scope.raw)
+            out0 = alloc_out(shape(m), torch.float32, dev)
+            out1 = None if a1 is None else alloc_out(shape(m), torch.float32, dev)
+            scope.keep(pos, h, a0, a1, *more, *cols, out1)
+            call(True, pos, h, a0, a1, more, n, cols, m, out0, out1, dev.index or 0, scope.raw)
         return out0
     pos, n, _ = positions_f64(positions, cast=False)
     h, a0, a1 = (None if a is None else host_f64(a, name, (n,), cast=False) for a, name in fields)
+    more = [host_f64(a, name, (n,), cast=False) for a, name in extra]
     pts = np.asarray(points)
     if pts.ndim != 2 or pts.shape[1] not in widths:
         raise ValueError(f"points must have shape {shapes}, got {pts.shape}")
@@ -195,12 +206,12 @@ def sample_sums(entry, lead, positions, smoothing_lengths, particle_properties, 
     m = pts.shape[0]
     if a1 is not None:
         a0 = a0 * a1
-    out0 = alloc_out((m,), np.float32, None, zeros=True)
-    out1 = None if a1 is None else alloc_out((m,), np.float32, None, zeros=True)
+    out0 = alloc_out(shape(m), np.float32, None, zeros=True)
+    out1 = None if a1 is None else alloc_out(shape(m), np.float32, None, zeros=True)
     if m == 0:
         return out0
     _lib.require_gpu(device)
-    call(False, pos, h, a0, a1, n, cols, m, out0, out1, device, None)
+    call(False, pos, h, a0, a1, more, n, cols, m, out0, out1, device, None)
     return out0
 
 

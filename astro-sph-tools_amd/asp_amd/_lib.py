@@ -48,6 +48,10 @@ STAGES = ("memset", "count", "colscan", "tilescan", "scatter", "scale", "deposit
 # asp_sample2d's stages, numbered after STAGES (21, 22)
 SAMPLE_STAGES = ("sample_prep", "sample_deposit")
 ALL_STAGES = STAGES + SAMPLE_STAGES
+# asp_spectra2d's deposit (23; its prep is sample_prep), after ALL_STAGES
+SPECTRA_STAGES = ("spectra_deposit",)
+PROFILE_STAGES = ALL_STAGES + SPECTRA_STAGES  # every stage profile() / profile_read() know
+SPECTRA_T = 5.0  # ASP_SPECTRA_T of include/asp_spectra.h
 
 _lib = None
 
@@ -115,6 +119,12 @@ POINT_PROTOTYPES = {
 PROFILE_PROTOTYPES = {
     "asp_halo_profiles": [_d, _d, _I, _Q, _d, _d, _Q, _d, _I, _R, _i64, _d, _I, _I, _V],
 }
+# The C-ABI of include/asp_spectra.h (sightline spectra).
+_VELBINS = [_R, _R, _I, _I]  # v0, dv, nbins, ring
+SPECTRA_PROTOTYPES = {
+    "asp_spectra2d": [_f] * 5 + [_d, _f, _Q, _d, _d, _Q] + _VELBINS + [_I, _I, _f, _f, _I, _V],
+    "asp_spectra2d_f64": [_d] * 6 + [_Q, _I, _d, _d, _Q] + _VELBINS + [_I, _I, _f, _f, _I, _V],
+}
 
 
 class ASPError(RuntimeError):
@@ -141,7 +151,8 @@ def lib():
         except Exception:
             pass
     L = C.CDLL(LIB_PATH)
-    for name, argtypes in {**PROTOTYPES, **POINT_PROTOTYPES, **PROFILE_PROTOTYPES}.items():
+    for name, argtypes in {**PROTOTYPES, **POINT_PROTOTYPES, **PROFILE_PROTOTYPES,
+                           **SPECTRA_PROTOTYPES}.items():
         fn = getattr(L, name, None)  # (absent from an older A/B build, ASP_LIB)
         if fn is not None:
             fn.argtypes, fn.restype = argtypes, RESTYPES.get(name, C.c_int)
@@ -191,19 +202,19 @@ def last_stats(device: int = 0):
 
 def profile(device: int = 0, enable: bool = True, stages=None):
     """Start (and reset) / stop per-stage HIP-event timing inside the library; ``stages``
-    (names of ALL_STAGES) limits the events to those stages."""
+    (names of PROFILE_STAGES) limits the events to those stages."""
     if stages is None or not enable:
         check(lib().asp_profile(device, 1 if enable else 0))
     else:
         mask = 0
         for s in stages:
-            mask |= 1 << ALL_STAGES.index(s)
+            mask |= 1 << PROFILE_STAGES.index(s)
         check(lib().asp_profile_stages(device, mask))
 
 
 def profile_read(device: int = 0):
     """{stage: (total_ms, launches)} since the last reset."""
-    ms = (C.c_double * len(ALL_STAGES))()
-    n = (C.c_int64 * len(ALL_STAGES))()
-    check(lib().asp_profile_read(device, ms, n, len(ALL_STAGES)))
-    return {s: (ms[i], n[i]) for i, s in enumerate(ALL_STAGES)}
+    ms = (C.c_double * len(PROFILE_STAGES))()
+    n = (C.c_int64 * len(PROFILE_STAGES))()
+    check(lib().asp_profile_read(device, ms, n, len(PROFILE_STAGES)))
+    return {s: (ms[i], n[i]) for i, s in enumerate(PROFILE_STAGES)}

@@ -73,7 +73,7 @@ struct Buf {
     size_t cap = 0;
 };
 
-constexpr int kStages = 23;
+constexpr int kStages = 24;
 constexpr int kNStats = 16;  // asp_last_stats
 constexpr int kMarks = 8;  // launches of one stage timed per call
 enum Stage {
@@ -86,7 +86,9 @@ enum Stage {
     // asp_nearest: centre check / cell sort; the search (with the query sort, when on)
     kSNearestPrep = 19, kSNearestSearch = 20,
     // asp_sample2d: point keys / sort / cell offsets; the particle -> point deposit
-    kSSamplePrep = 21, kSSampleDeposit = 22
+    kSSamplePrep = 21, kSSampleDeposit = 22,
+    // asp_spectra2d: the (pair, velocity bin) deposit and its finalising pass (its prep: 21)
+    kSSpectraDeposit = 23
 };
 
 // What the slots of the workspace's buffer arrays hold (Workspace::knn, nearest, match,
@@ -141,6 +143,7 @@ enum SampleBuf {
     kSmpSorted,                // point coordinates in cell order (x, then y, then z in 3-D)
     kSmpAcc,                   // per-point accumulators (fp64 or int64), in cell order
     kSmpPz,                    // staged third point coordinate (3-D)
+    kSmpVc, kSmpB,             // asp_spectra2d: staged velocity coordinates and Doppler parameters
     kSampleBufCount
 };
 // asp_halo_profiles

@@ -36,8 +36,9 @@
 //     atomics (-munsafe-fp-atomics: the hardware L2 fp64 add).
 //   finalise: one pass converts to fp32, applies ratio / accumulate (emit_pixel, the map's)
 //     and writes in the caller's point order.
-// This unit holds k_sample's walk and the 2-D grid rule and thresholds; the rest is
-// asp_sample.hpp, shared with the 3-D sampler (asp_sample3d.hip).
+// This unit holds k_sample's walk and the 2-D grid rule; the rest is asp_sample.hpp, shared
+// with the 3-D sampler (asp_sample3d.hip) and, with the 2-D thresholds, with the spectra
+// (asp_spectra.hip).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -47,11 +48,6 @@
 #include "asp_sample.hpp"
 
 namespace asp {
-
-constexpr int kSampleMaxG = 2048;     // cells per axis at most: a 16 MiB cell-start table
-constexpr int kSamplePerCell = 4;     // points per cell the grid aims at
-constexpr int kSampleWideCells = 16;  // boxes over more cells go to the wave (ASP_SAMPLE_WIDE_CELLS)
-constexpr int kSampleWidePoints = 256;  // ... and boxes holding more points (ASP_SAMPLE_WIDE_POINTS)
 
 template <int KID, int NOUT, int ACC, bool F64>
 __global__ __launch_bounds__(kSBlock) void k_sample(const Part<2> P, long long n,

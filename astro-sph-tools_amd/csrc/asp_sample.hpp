@@ -1,7 +1,8 @@
 // asp_sample.hpp -- the point grid of the 2-D sampler (asp_sample.hip, DIM = 2) and of the
 // 3-D sampler (asp_sample3d.hip, DIM = 3), written once: the descriptor and its prep kernels,
 // the particle loader, the fixed-point scale passes, a particle's record and cell range, the
-// pair test, the finalising pass, the argument checks and the host driver of a call.  A unit
+// pair test, the finalising pass, the argument checks, the prep and the particle staging of a
+// call and the samplers' host driver (asp_spectra.hip has its own, over the same prep).  A unit
 // keeps what rests on its own measurements: its deposit kernel's walk
 // over the cell range, the grid-size rule, the thresholds and the kernel-id range.
 #pragma once
@@ -20,6 +21,13 @@
 namespace asp {
 
 constexpr int kSBlock = 256;
+
+// The grid rule and the class thresholds over 2-D points (measured in DESIGN.md §20), for the
+// units that walk them: asp_sample.hip and asp_spectra.hip.
+constexpr int kSampleMaxG = 2048;     // cells per axis at most: a 16 MiB cell-start table
+constexpr int kSamplePerCell = 4;     // points per cell the grid aims at
+constexpr int kSampleWideCells = 16;  // boxes over more cells go to the wave (ASP_SAMPLE_WIDE_CELLS)
+constexpr int kSampleWidePoints = 256;  // ... and boxes holding more points (ASP_SAMPLE_WIDE_POINTS)
 
 // fp64 <-> unsigned with the same order (for atomicMin / atomicMax).
 __device__ __forceinline__ unsigned long long enc_ordered(double d) {
@@ -346,15 +354,22 @@ __device__ __forceinline__ Span from_lane(const Span& c, int l) {
 // One (particle, point) pair: the reference's test (.pyx:20-31; the cube's voxel_pass), and
 // the term if it passes.  r2 is summed left to right, dx dx + dy dy (+ dz dz), without
 // contraction (-ffp-contract=off).
-template <int DIM, int KID, int NOUT, int ACC>
-__device__ __forceinline__ void pair(const Rec<DIM>& R, const Points<DIM>& S, int j) {
+template <int DIM, int KID>
+__device__ __forceinline__ bool pair_shape(const Rec<DIM>& R, const Points<DIM>& S, int j, float& w) {
     double dd[DIM];
     for (int d = 0; d < DIM; ++d) dd[d] = R.C[d] - S.s[d][j];
     double r2 = dd[0] * dd[0];
     for (int d = 1; d < DIM; ++d) r2 = r2 + dd[d] * dd[d];
-    if (r2 < R.T2) {
-        const float q = __builtin_amdgcn_sqrtf((float)r2) * R.hinv;
-        const float w = kernel_shape<KID>(q);
+    if (!(r2 < R.T2)) return false;
+    const float q = __builtin_amdgcn_sqrtf((float)r2) * R.hinv;
+    w = kernel_shape<KID>(q);
+    return true;
+}
+// ... its terms s w added to the point's accumulators (the samplers' deposit).
+template <int DIM, int KID, int NOUT, int ACC>
+__device__ __forceinline__ void pair(const Rec<DIM>& R, const Points<DIM>& S, int j) {
+    float w;
+    if (pair_shape<DIM, KID>(R, S, j, w)) {
         acc_add<ACC>(&S.acc[j], R.s0 * w);
         if constexpr (NOUT == 2) acc_add<ACC>(&S.acc[S.m + j], R.s1 * w);
     }
@@ -436,6 +451,137 @@ int sample_check(const SampleArgs<DIM>& A, bool f64) {
     return ASP_OK;
 }
 
+// The particle arrays [a, b) of a call as the deposit kernel reads them: the caller's device
+// arrays, or a host caller's batch staged through the kSmpPart slots -- the fp64 arrays one
+// slot each; the fp32 coordinates, then h, then both amplitudes sharing the last.
+template <int DIM, bool F64>
+int stage_batch(Workspace& ws, const SampleArgs<DIM>& A, long long a, long long b, hipStream_t st,
+                Part<DIM>& P) {
+    const bool dev = A.flags & ASP_F_DEVICE_PTRS;
+    Buf* B = ws.sample;
+    const size_t nb = (size_t)(b - a);
+    P = Part<DIM>{};
+    if constexpr (F64) {
+        if constexpr (DIM == 2) {
+            const int cols[3][2] = {{1, 2}, {0, 2}, {0, 1}};  // _projector.py:38-46
+            P.col[0] = cols[A.axis][0];
+            P.col[1] = cols[A.axis][1];
+        }
+        P.pos = A.src.pos + 3 * a;
+        P.h64 = A.src.h64 + a;
+        P.a064 = A.src.a064 + a;
+        P.a164 = A.src.a164 ? A.src.a164 + a : nullptr;
+        const double** arr[4] = {&P.pos, &P.h64, &P.a064, &P.a164};
+        for (int i = 0; i < 4; ++i)
+            if (!dev && *arr[i])
+                ASP_TRY(to_device(ws, B[kSmpPart0 + i], *arr[i], nb * (i ? 1 : 3) * sizeof(double),
+                                  st, Copy::kPinned));
+    } else {
+        const float** arr[DIM + 3];  // array i goes to slot min(i, DIM + 1), a1 behind a0
+        for (int d = 0; d < DIM; ++d) {
+            P.c[d] = A.src.c[d] + a;
+            arr[d] = &P.c[d];
+        }
+        P.h = A.src.h + a;
+        P.a0 = A.src.a0 + a;
+        P.a1 = A.src.a1 ? A.src.a1 + a : nullptr;
+        arr[DIM] = &P.h;
+        arr[DIM + 1] = &P.a0;
+        arr[DIM + 2] = &P.a1;
+        const size_t fb = nb * sizeof(float);
+        float* both = nullptr;  // the last slot is sized for both amplitudes first
+        if (!dev) ASP_TRY(device_scratch(B[kSmpPart0 + DIM + 1], both, 2 * fb));
+        for (int i = 0; i < DIM + 3; ++i)
+            if (!dev && *arr[i])
+                ASP_TRY(to_device(ws, B[kSmpPart0 + std::min(i, DIM + 1)], *arr[i], fb, st,
+                                  Copy::kPinned, i == DIM + 2 ? fb : 0));
+    }
+    return ASP_OK;
+}
+
+// What the prep leaves for the deposit and the finalising pass: the descriptor, the cells per
+// axis, the sorted points and their accumulators, the permutation (cell order -> the caller's
+// order), the grid of a pass over the points and the device outputs.
+template <int DIM>
+struct SGrid {
+    SDescT<DIM>* D;
+    int G;
+    Points<DIM> S;
+    const int* perm;
+    unsigned pgrid;
+    float *d0, *d1;
+};
+
+// The prep of a call (stage sample_prep): the points on the device, keyed, sorted, their cells
+// scanned; `width` accumulators per point and sum (the samplers: 1, zeroed here; a unit with
+// more zeroes them itself) and as many output values.
+template <int DIM, class TR>
+int sample_prep(Workspace& ws, hipStream_t st, const SampleArgs<DIM>& A, size_t width, SGrid<DIM>& g) {
+    using Desc = SDescT<DIM>;
+    const bool dev = A.flags & ASP_F_DEVICE_PTRS;
+    const bool acc_flag = A.flags & ASP_F_ACCUMULATE;
+    const int nout = A.out1 ? 2 : 1;
+    const long long m = A.m;
+    const size_t pbytes = (size_t)m * sizeof(double), obytes = (size_t)m * width * sizeof(float);
+    Buf* B = ws.sample;
+    StageMark mprep(ws, kSSamplePrep, st);
+    Coords<DIM> X = A.pt;
+    float *d0 = A.out0, *d1 = A.out1;
+    if (!dev) {
+        const int slot[3] = {kSmpPx, kSmpPy, kSmpPz};
+        for (int d = 0; d < DIM; ++d)
+            ASP_TRY(to_device(ws, B[slot[d]], X.c[d], pbytes, st, Copy::kPlain));
+        ASP_TRY(device_scratch(B[kSmpOut0], d0, obytes));
+        if (A.out1) ASP_TRY(device_scratch(B[kSmpOut1], d1, obytes));
+        if (acc_flag) {
+            ASP_HIP(hipMemcpyAsync(d0, A.out0, obytes, hipMemcpyHostToDevice, st));
+            if (d1) ASP_HIP(hipMemcpyAsync(d1, A.out1, obytes, hipMemcpyHostToDevice, st));
+        }
+    }
+    const int G = (int)env_int("ASP_SAMPLE_CELLS", std::max(1, std::min(TR::kMaxG, TR::cells(m))), 1,
+                               TR::kMaxG);
+    size_t ncell = 1;  // G^DIM cells and one more: points with a non-finite coordinate
+    for (int d = 0; d < DIM; ++d) ncell *= (size_t)G;
+    int key_bits = 1;
+    while ((1ull << key_bits) <= ncell) ++key_bits;
+    ++ncell;
+    Desc* D = nullptr;
+    unsigned* kin = nullptr;
+    int *iin = nullptr, *cnt = nullptr, *start = nullptr;
+    double* sorted = nullptr;
+    unsigned long long* acc = nullptr;
+    ASP_TRY(device_scratch(B[kSmpDesc], D, sizeof(Desc)));
+    ASP_TRY(device_scratch(B[kSmpKeys], kin, (size_t)m * 2 * sizeof(unsigned)));
+    ASP_TRY(device_scratch(B[kSmpIndex], iin, (size_t)m * 2 * sizeof(int)));
+    ASP_TRY(device_scratch(B[kSmpCellCount], cnt, (ncell + 1) * sizeof(int)));
+    ASP_TRY(device_scratch(B[kSmpCellStart], start, (ncell + 1) * sizeof(int)));
+    ASP_TRY(device_scratch(B[kSmpSorted], sorted, DIM * pbytes));
+    ASP_TRY(device_scratch(B[kSmpAcc], acc, (size_t)nout * m * width * sizeof(unsigned long long)));
+    unsigned* kout = kin + m;
+    const int* iout = iin + m;
+    Points<DIM> S{start, {}, m, acc};
+    for (int d = 0; d < DIM; ++d) S.s[d] = sorted + d * m;
+    const unsigned pgrid = (unsigned)((m + kSBlock - 1) / kSBlock);
+    hipLaunchKernelGGL(k_sinit<DIM>, dim3(1), dim3(1), 0, st, D);
+    ASP_LAUNCHED();
+    hipLaunchKernelGGL(k_sbbox<DIM>, dim3(pgrid), dim3(kSBlock), 0, st, X, m, D);
+    ASP_LAUNCHED();
+    hipLaunchKernelGGL(k_sdesc<DIM>, dim3(1), dim3(1), 0, st, D, G);
+    ASP_LAUNCHED();
+    ASP_HIP(hipMemsetAsync(cnt, 0, (ncell + 1) * sizeof(int), st));
+    hipLaunchKernelGGL(k_skeys<DIM>, dim3(pgrid), dim3(kSBlock), 0, st, X, m, (const Desc*)D, G, kin,
+                       iin, cnt);
+    ASP_LAUNCHED();
+    ASP_TRY(sort_pairs(B[kSmpSortTmp], kin, kout, iin, iin + m, (size_t)m, key_bits, st));
+    ASP_TRY(exclusive_scan_int(B[kSmpScanTmp], cnt, start, ncell + 1, st));
+    hipLaunchKernelGGL((nout == 2 ? k_sgather<DIM, 2> : k_sgather<DIM, 1>), dim3(pgrid), dim3(kSBlock),
+                       0, st, X, m, iout, sorted, acc);
+    ASP_LAUNCHED();
+    mprep.done();
+    g = SGrid<DIM>{D, G, S, iout, pgrid, d0, d1};
+    return ASP_OK;
+}
+
 // One call: the points staged, keyed and sorted (stage sample_prep); the particles, batch by
 // batch, through the unit's deposit kernel into the points' accumulators (stage
 // sample_deposit); the accumulators converted and written in the caller's order.
@@ -448,7 +594,7 @@ int sample_driver(const SampleArgs<DIM>& A, int device, hipStream_t stream) {
     const bool acc_flag = A.flags & ASP_F_ACCUMULATE;
     const int nout = A.out1 ? 2 : 1;
     const long long m = A.m, n = A.n;
-    const size_t pbytes = (size_t)m * sizeof(double), obytes = (size_t)m * sizeof(float);
+    const size_t obytes = (size_t)m * sizeof(float);
     if (n == 0 && (acc_flag || !dev)) {  // nothing to add; host outputs need no device
         if (!acc_flag) {
             memset(A.out0, 0, obytes);
@@ -467,107 +613,18 @@ int sample_driver(const SampleArgs<DIM>& A, int device, hipStream_t stream) {
         }
         const bool det = A.flags & ASP_F_DETERMINISTIC;
         const bool count = env_set("ASP_SAMPLE_COUNT");
-        Buf* B = ws.sample;
 
         // ---- prep: the points on the device, keyed, sorted, their cells scanned ----
-        StageMark mprep(ws, kSSamplePrep, st);
-        Coords<DIM> X = A.pt;
-        float *d0 = A.out0, *d1 = A.out1;
-        if (!dev) {
-            const int slot[3] = {kSmpPx, kSmpPy, kSmpPz};
-            for (int d = 0; d < DIM; ++d)
-                ASP_TRY(to_device(ws, B[slot[d]], X.c[d], pbytes, st, Copy::kPlain));
-            ASP_TRY(device_scratch(B[kSmpOut0], d0, obytes));
-            if (A.out1) ASP_TRY(device_scratch(B[kSmpOut1], d1, obytes));
-            if (acc_flag) {
-                ASP_HIP(hipMemcpyAsync(d0, A.out0, obytes, hipMemcpyHostToDevice, st));
-                if (d1) ASP_HIP(hipMemcpyAsync(d1, A.out1, obytes, hipMemcpyHostToDevice, st));
-            }
-        }
-        const int G = (int)env_int("ASP_SAMPLE_CELLS", std::max(1, std::min(TR::kMaxG, TR::cells(m))), 1,
-                                   TR::kMaxG);
+        SGrid<DIM> g;
+        ASP_TRY((sample_prep<DIM, TR>(ws, st, A, 1, g)));
+        Desc* const D = g.D;
+        const int G = g.G;
+        const Points<DIM>& S = g.S;
         const typename TR::Knobs knobs = TR::knobs();
-        size_t ncell = 1;  // G^DIM cells and one more: points with a non-finite coordinate
-        for (int d = 0; d < DIM; ++d) ncell *= (size_t)G;
-        int key_bits = 1;
-        while ((1ull << key_bits) <= ncell) ++key_bits;
-        ++ncell;
-        Desc* D = nullptr;
-        unsigned* kin = nullptr;
-        int *iin = nullptr, *cnt = nullptr, *start = nullptr;
-        double* sorted = nullptr;
-        unsigned long long* acc = nullptr;
-        ASP_TRY(device_scratch(B[kSmpDesc], D, sizeof(Desc)));
-        ASP_TRY(device_scratch(B[kSmpKeys], kin, (size_t)m * 2 * sizeof(unsigned)));
-        ASP_TRY(device_scratch(B[kSmpIndex], iin, (size_t)m * 2 * sizeof(int)));
-        ASP_TRY(device_scratch(B[kSmpCellCount], cnt, (ncell + 1) * sizeof(int)));
-        ASP_TRY(device_scratch(B[kSmpCellStart], start, (ncell + 1) * sizeof(int)));
-        ASP_TRY(device_scratch(B[kSmpSorted], sorted, DIM * pbytes));
-        ASP_TRY(device_scratch(B[kSmpAcc], acc, (size_t)nout * m * sizeof(unsigned long long)));
-        unsigned* kout = kin + m;
-        const int* iout = iin + m;
-        Points<DIM> S{start, {}, m, acc};
-        for (int d = 0; d < DIM; ++d) S.s[d] = sorted + d * m;
-        const unsigned pgrid = (unsigned)((m + kSBlock - 1) / kSBlock);
-        hipLaunchKernelGGL(k_sinit<DIM>, dim3(1), dim3(1), 0, st, D);
-        ASP_LAUNCHED();
-        hipLaunchKernelGGL(k_sbbox<DIM>, dim3(pgrid), dim3(kSBlock), 0, st, X, m, D);
-        ASP_LAUNCHED();
-        hipLaunchKernelGGL(k_sdesc<DIM>, dim3(1), dim3(1), 0, st, D, G);
-        ASP_LAUNCHED();
-        ASP_HIP(hipMemsetAsync(cnt, 0, (ncell + 1) * sizeof(int), st));
-        hipLaunchKernelGGL(k_skeys<DIM>, dim3(pgrid), dim3(kSBlock), 0, st, X, m, (const Desc*)D, G, kin,
-                           iin, cnt);
-        ASP_LAUNCHED();
-        ASP_TRY(sort_pairs(B[kSmpSortTmp], kin, kout, iin, iin + m, (size_t)m, key_bits, st));
-        ASP_TRY(exclusive_scan_int(B[kSmpScanTmp], cnt, start, ncell + 1, st));
-        hipLaunchKernelGGL((nout == 2 ? k_sgather<DIM, 2> : k_sgather<DIM, 1>), dim3(pgrid), dim3(kSBlock),
-                           0, st, X, m, iout, sorted, acc);
-        ASP_LAUNCHED();
-        mprep.done();
 
         // ---- the particles, batch by batch, into the same accumulators ----
-        // A host caller's batch is staged through the kSmpPart slots: the fp64 arrays one
-        // slot each; the fp32 coordinates, then h, then both amplitudes sharing the last.
         auto stage = [&](long long a, long long b, Part<DIM>& P) -> int {
-            const size_t nb = (size_t)(b - a);
-            P = Part<DIM>{};
-            if constexpr (F64) {
-                if constexpr (DIM == 2) {
-                    const int cols[3][2] = {{1, 2}, {0, 2}, {0, 1}};  // _projector.py:38-46
-                    P.col[0] = cols[A.axis][0];
-                    P.col[1] = cols[A.axis][1];
-                }
-                P.pos = A.src.pos + 3 * a;
-                P.h64 = A.src.h64 + a;
-                P.a064 = A.src.a064 + a;
-                P.a164 = A.src.a164 ? A.src.a164 + a : nullptr;
-                const double** arr[4] = {&P.pos, &P.h64, &P.a064, &P.a164};
-                for (int i = 0; i < 4; ++i)
-                    if (!dev && *arr[i])
-                        ASP_TRY(to_device(ws, B[kSmpPart0 + i], *arr[i], nb * (i ? 1 : 3) * sizeof(double),
-                                          st, Copy::kPinned));
-            } else {
-                const float** arr[DIM + 3];  // array i goes to slot min(i, DIM + 1), a1 behind a0
-                for (int d = 0; d < DIM; ++d) {
-                    P.c[d] = A.src.c[d] + a;
-                    arr[d] = &P.c[d];
-                }
-                P.h = A.src.h + a;
-                P.a0 = A.src.a0 + a;
-                P.a1 = A.src.a1 ? A.src.a1 + a : nullptr;
-                arr[DIM] = &P.h;
-                arr[DIM + 1] = &P.a0;
-                arr[DIM + 2] = &P.a1;
-                const size_t fb = nb * sizeof(float);
-                float* both = nullptr;  // the last slot is sized for both amplitudes first
-                if (!dev) ASP_TRY(device_scratch(B[kSmpPart0 + DIM + 1], both, 2 * fb));
-                for (int i = 0; i < DIM + 3; ++i)
-                    if (!dev && *arr[i])
-                        ASP_TRY(to_device(ws, B[kSmpPart0 + std::min(i, DIM + 1)], *arr[i], fb, st,
-                                          Copy::kPinned, i == DIM + 2 ? fb : 0));
-            }
-            return ASP_OK;
+            return stage_batch<DIM, F64>(ws, A, a, b, st, P);
         };
         if (det) {  // the scale needs max |c| over ALL particles before the first term
             ASP_TRY(for_batches(n, [&](long long a, long long b, int) -> int {
@@ -605,16 +662,16 @@ int sample_driver(const SampleArgs<DIM>& A, int device, hipStream_t stream) {
         const int kflags = (acc_flag ? kFlagAccumulate : 0) | ((A.flags & ASP_F_RATIO) ? kFlagRatio : 0);
         StageMark mfin(ws, kSSampleDeposit, st);
         ASP_TRY(TR::dispatch(0, nout, det, [&](auto, auto NO, auto AC) -> int {
-            hipLaunchKernelGGL((k_sfinal<DIM, decltype(NO)::value, decltype(AC)::value>), dim3(pgrid),
-                               dim3(kSBlock), 0, st, (const unsigned long long*)acc, m, iout, (const Desc*)D,
-                               d0, d1, kflags);
+            hipLaunchKernelGGL((k_sfinal<DIM, decltype(NO)::value, decltype(AC)::value>), dim3(g.pgrid),
+                               dim3(kSBlock), 0, st, (const unsigned long long*)S.acc, m, g.perm,
+                               (const Desc*)D, g.d0, g.d1, kflags);
             ASP_LAUNCHED();
             return ASP_OK;
         }));
         mfin.done();
         if (!dev) {
-            ASP_TRY(to_host(A.out0, d0, obytes, st));
-            if (A.out1) ASP_TRY(to_host(A.out1, d1, obytes, st));
+            ASP_TRY(to_host(A.out0, g.d0, obytes, st));
+            if (A.out1) ASP_TRY(to_host(A.out1, g.d1, obytes, st));
         }
         if (count) {
             unsigned long long e = 0;

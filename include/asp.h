@@ -579,7 +579,8 @@ int asp_table_interp(const double *table, int32_t ndim, const int32_t *shape,
  * tiles and batched calls: the sums over all passes.  After asp_knn_smoothing_lengths
  * (ASP_KNN_COUNT) and asp_nearest (ASP_NEAREST_COUNT) the words describe that call: stats[9]
  * = distances evaluated (asp_nearest: over all queries and sets), the map counters 0; after
- * asp_sample2d(_f64) with ASP_SAMPLE_COUNT stats[9] = (particle, point) pairs tested.
+ * asp_sample2d(_f64) with ASP_SAMPLE_COUNT stats[9] = (particle, point) pairs tested;
+ * after asp_spectra2d(_f64) with it, stats[10] = (pair, bin) adds issued as well.
  */
 int asp_last_stats(int32_t device, int64_t *stats, int32_t nstats);
 
@@ -593,7 +594,9 @@ int asp_last_stats(int32_t device, int64_t *stats, int32_t nstats);
  * 17 knn_prep, 18 knn_search (asp_knn_smoothing_lengths); 19 nearest_prep, 20 nearest_search
  * (asp_nearest: the centre check and cell sort; the search, with the query sort when on);
  * 21 sample_prep, 22 sample_deposit (asp_sample2d: point keys, sort and cell offsets; the
- * particle -> point deposit with the fixed-point scale and the finalising pass).
+ * particle -> point deposit with the fixed-point scale and the finalising pass);
+ * 23 spectra_deposit (asp_spectra2d, asp_spectra.h: the (pair, velocity bin) deposit and its
+ * finalising pass; its prep is stage 21).
  */
 int asp_profile(int32_t device, int32_t enable);
 /* As asp_profile(device, 1), but events only around the stages whose bit is set in
