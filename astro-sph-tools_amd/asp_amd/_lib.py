@@ -192,10 +192,16 @@ def ptr(a, t=_f):
 
 
 def last_stats(device: int = 0):
+    """The words of asp_last_stats (include/asp.h) by name.  After a k-NN call with
+    ASP_KNN_COUNT: ``evals`` window distances, ``evals_small`` per-lane cell-scan distances,
+    ``evals_gather`` entries the shared cell pass streamed, ``evals_wide`` top-k insertions,
+    ``knn_fallbacks`` (the word of ``large``) waves whose shared cell pass fell back to the
+    per-lane pass."""
     s = (C.c_int64 * 16)()
     check(lib().asp_last_stats(device, s, 16))
     return {"records": s[0], "items": s[1], "wide": s[2], "tile": s[3], "tiles": s[4],
             "records_per_item": s[5], "merges": s[6], "slabs": s[7], "large": s[8],
+            "knn_fallbacks": s[8],
             "evals": s[9], "evals_small": s[10], "evals_gather": s[11], "evals_wide": s[12],
             "scatter_path": s[13], "placement_runs": s[14], "layout_reuse": s[15]}
 

@@ -20,6 +20,12 @@ def knn_smoothing_lengths(positions, k: int = 32, *, device: int = 0, stream=Non
     ``positions``: (N, 3) float64 -- a NumPy (or unyt) host array, returning a NumPy
     array, or a float64 torch tensor on the GPU, returning a tensor there.  ``inf`` where
     fewer than k particles exist (as scipy reports a missing neighbour).
+
+    Non-finite values (scipy raises; here they are defined): a row with a NaN or infinite
+    coordinate is nobody's neighbour and gets ``inf``; every other row gets its k-th smallest
+    finite squared distance among the rows with a position, or ``inf`` if fewer than k are
+    finite (too few such rows, or squares that overflow) -- what scipy returns for the finite
+    rows alone.
     """
     k = int(k)
     if is_device(positions):

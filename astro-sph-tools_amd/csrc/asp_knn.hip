@@ -5,7 +5,9 @@
 // neighbour, the particle itself counted (k = 32 there).  The distance is scipy's
 // Euclidean one in fp64, d2 = ((x_i - x_j)^2 + (y_i - y_j)^2) + (z_i - z_j)^2 and
 // h = sqrt(d2_(k)), so results are bit-identical to the reference (tests/test_gpu_knn.py);
-// +inf when n < k (scipy's value for a missing neighbour).
+// +inf when n < k (scipy's value for a missing neighbour).  A row with a non-finite coordinate
+// is nobody's neighbour and gets +inf; a row with fewer than k finite d2 gets +inf; every
+// lane's work is bounded by n for any input bits.
 //
 // MI355X layout: particles sorted along a 63-bit Morton curve (21 bits per axis over the
 // bounding cube; rocPRIM radix sort), positions gathered into sorted fp64 SoA.  One wave
@@ -60,7 +62,7 @@ __device__ __forceinline__ unsigned long long morton3(long long a, long long b, 
     return (spread21(a) << 2) | (spread21(b) << 1) | spread21(c);
 }
 
-// Per-block min / max of each coordinate (NaN ignored) -> part[block][6].
+// Per-block min / max of each coordinate (NaN and +-inf ignored) -> part[block][6].
 __global__ __launch_bounds__(kKnnBlock) void k_bbox(const double* __restrict__ pos, long long n,
                                                     double* __restrict__ part) {
     __shared__ double s[6][kKnnBlock];
@@ -70,6 +72,7 @@ __global__ __launch_bounds__(kKnnBlock) void k_bbox(const double* __restrict__ p
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             double x = pos[3 * i + a];
+            if (!__builtin_isfinite(x)) continue;  // the grid spans the finite coordinates
             m[a] = fmin(m[a], x);
             m[3 + a] = fmax(m[3 + a], x);
         }
@@ -155,9 +158,25 @@ __global__ __launch_bounds__(kKnnBlock) void k_gather(const double* __restrict__
     long long i = (long long)blockIdx.x * kKnnBlock + threadIdx.x;
     if (i >= n) return;
     long long p = idx[i];
-    xs[i] = pos[3 * p];
-    ys[i] = pos[3 * p + 1];
-    zs[i] = pos[3 * p + 2];
+    const double x = pos[3 * p], y = pos[3 * p + 1], z = pos[3 * p + 2];
+    // a row with a non-finite coordinate is nobody's neighbour: all three NaN, so every
+    // distance to or from it is NaN, which no top-k takes (insert() admits only d < mx) and
+    // no fp32 bound passes; the search tells such a row by x != x
+    const bool fin = __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z);
+    const double nan = __builtin_nan("");
+    xs[i] = fin ? x : nan;
+    ys[i] = fin ? y : nan;
+    zs[i] = fin ? z : nan;
+}
+
+// The Morton level of a ball's cells: e with 2^e > qr = (radius in quanta) + 1, at most kQBits
+// (one cell: the whole cube).  A radius that is not finite -- fewer than k finite distances so
+// far -- takes kQBits as well; frexp's exponent of +inf or NaN is unspecified (0 on gfx950:
+// 2^21 cells per axis), so it is not asked.
+__device__ __forceinline__ int ball_level(double qr) {
+    int e = kQBits;
+    if (qr < (double)(1LL << kQBits)) frexp(qr, &e);
+    return e < kQBits ? e : kQBits;
 }
 
 // The k smallest d2 seen, in registers (static indexing only), kept sorted ascending in
@@ -455,9 +474,7 @@ __device__ __forceinline__ double knn_thread(long long i, const double* __restri
         const double R = sqrt(T.mx) * (1.0 + 0x1p-40);
         // cell edge 2^shift >= R + 1 quantum (in quanta), so the slackened ball spans at
         // most 3 cells per axis
-        int e;
-        frexp(R * G.scale + 1.0, &e);  // < 2^e
-        const int shift = std::min(e, kQBits);
+        const int shift = ball_level(R * G.scale + 1.0);  // R + 1 quantum < 2^shift quanta
         const double c[3] = {x, y, z};
         long long ca[3], cb[3], co[3];
 #pragma unroll
@@ -499,6 +516,11 @@ __device__ __forceinline__ double knn_thread(long long i, const double* __restri
                             T.insert(dist2(x, y, z, xs[j], ys[j], zs[j]));
                     }
         }
+    } else if (x == x && n >= k) {
+        // fewer than k finite distances inside the cell (rows without a position, or squares
+        // that overflow): no radius to search by -- the rest of the array, once
+        for (long long j = 0; j < w0; ++j) T.insert(dist2(x, y, z, xs[j], ys[j], zs[j]));
+        for (long long j = w1; j < n; ++j) T.insert(dist2(x, y, z, xs[j], ys[j], zs[j]));
     }
     return T.mx;
 }
@@ -647,13 +669,16 @@ __device__ __forceinline__ double dpp_d(double v, int which) {
     }
     return __builtin_bit_cast(double, ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
 }
-__device__ __forceinline__ double wave_max(double v) {  // v >= 0 or NaN-free
+__device__ __forceinline__ double read_lane(double v, int l) {  // lane l's v (l wave-uniform)
+    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
+    const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)b, l);
+    const unsigned hi = __builtin_amdgcn_readlane((int)(unsigned)(b >> 32), l);
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ double wave_max(double v) {  // of the lanes that are not NaN (fmax)
 #pragma unroll
     for (int w = 0; w < 6; ++w) v = fmax(v, dpp_d(v, w));
-    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
-    const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)b, 63);
-    const unsigned hi = __builtin_amdgcn_readlane((int)(unsigned)(b >> 32), 63);
-    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+    return read_lane(v, 63);
 }
 
 // The window pass with an fp32 prefilter.  Entries go to LDS twice: fp64 (for the exact
@@ -679,7 +704,10 @@ __device__ __forceinline__ void wave_stream32(long long nent, At at, const doubl
                                               double* lz, float* fx, float* fy, float* fz, int lane,
                                               double x, double y, double z, bool part, TopK<K>& T,
                                               bool fill = false, int sdiag = 0) {
-    const double ox = __shfl(x, 0, 64), oy = __shfl(y, 0, 64), oz = __shfl(z, 0, 64);
+    // the origin: the first lane with a position (k_gather: a row without one is NaN in x)
+    const unsigned long long fm = __ballot(x == x);
+    const int ol = fm ? __builtin_ctzll(fm) : 0;
+    const double ox = read_lane(x, ol), oy = read_lane(y, ol), oz = read_lane(z, ol);
     const double rx = x - ox, ry = y - oy, rz = z - oz;
     const float qx = (float)rx, qy = (float)ry, qz = (float)rz;
     const kf2 qx2 = {qx, qx}, qy2 = {qy, qy}, qz2 = {qz, qz};
@@ -718,14 +746,23 @@ __device__ __forceinline__ void wave_stream32(long long nent, At at, const doubl
             fz[lane] = 0.0f;
         }
         const double M = fmax(mq, wave_max(me));
-        wave_sync();
         const float Mf = (float)M * (1.0f + 0x1p-22f);  // >= M
+        // offsets beyond fp32's range (coordinates ~1e150): inf - inf is NaN, which no bound
+        // passes, so true neighbours were dropped.  The bound is +inf then (its M term), and
+        // every entry with a position is staged at the origin: all of them pass (|q - 0|^2 <=
+        // inf) and get their exact fp64 distance.  Entries without one keep their NaN.
+        if (!(Mf < INFINITY) && g >= 0 && ex == ex) fx[lane] = fy[lane] = fz[lane] = 0.0f;
+        wave_sync();
         auto bound = [&]() -> float {
             if (!part) return -1.0f;
             if (!(T.mx < INFINITY)) return INFINITY;
             if (T.mx < 0x1p-100) {  // fp32 would lose the radius: the fp64 form
                 const double r = sqrt(T.mx) * (1.0 + 0x1p-22) + 0x1p-21 * M;
-                return (float)(r * r * (1.0 + 0x1p-21)) * (1.0f + 0x1p-22f);
+                // never below 2^-99: a smaller bound is subnormal in fp32 (or near it), where
+                // it and d32 round to multiples of 2^-149, not to the relative accuracy the
+                // analysis rests on -- a true candidate's d32 could round up past a bound
+                // rounded down.  With r^2 < 2^-99 every true candidate has d32 < 2^-99.
+                return fmaxf((float)(r * r * (1.0 + 0x1p-21)) * (1.0f + 0x1p-22f), 0x1p-99f);
             }
             // the same bound in fp32 (round 6): sqrt of fl32(mx) is within ~2^-23 of
             // sqrt(mx); widened by 2^-18 (and Mf >= M (1 + 2^-23)), the fp32 sum is >= the
@@ -965,11 +1002,7 @@ __global__ __launch_bounds__(kKnnBlock, (K == 32 ? 3 : 1)) ASP_KNN_OCC void k_kn
         const bool ok = act && C.T.mx < INFINITY;
         const double R = sqrt(C.T.mx) * (1.0 + 0x1p-40);
         int sft = 99;  // this lane's own cell level (as the per-lane pass)
-        if (ok) {
-            int e;
-            frexp(R * G.scale + 1.0, &e);
-            sft = max(0, min(e, kQBits) - fine);
-        }
+        if (ok) sft = max(0, ball_level(R * G.scale + 1.0) - fine);
         const int nact = __popcll(__ballot(ok));
         if (nact > 0) {
             const int need = (nact * uq + 63) >> 6;
@@ -1049,11 +1082,6 @@ __global__ __launch_bounds__(kKnnBlock, (K == 32 ? 3 : 1)) ASP_KNN_OCC void k_kn
                     }
                 }
             }
-            if (evc && lane == 0) {  // diagnostic: columns and list entries of the shared pass
-                atomicAdd(&evc[4], (unsigned long long)ncol);
-                atomicAdd(&evc[5], (unsigned long long)nc);
-                atomicAdd(&evc[6], 1ULL);
-            }
             long long tot = 0;
             if (!ovf && nc > 0 && diag != 4) {
                 wave_sync();
@@ -1086,6 +1114,14 @@ __global__ __launch_bounds__(kKnnBlock, (K == 32 ? 3 : 1)) ASP_KNN_OCC void k_kn
                 }
                 wave_sync();
             }
+            if (evc && lane == 0) {  // diagnostic: columns and list entries of the shared pass
+                atomicAdd(&evc[4], (unsigned long long)ncol);
+                atomicAdd(&evc[5], (unsigned long long)nc);
+                atomicAdd(&evc[6], 1ULL);
+                // ... and the waves whose shared pass fell back to the per-lane pass: more
+                // than kUScan columns or kUCells ranges (ovf), or more than kUMaxEnt entries
+                if (ovf || tot > kUMaxEnt) atomicAdd(&evc[7], 1ULL);
+            }
             if (!ovf && tot <= kUMaxEnt && diag != 2 && diag != 4) {
                 const unsigned long long* L = ucl[wv];
                 int cur = 0;  // this lane's range of its previous entry (entries come in order)
@@ -1116,11 +1152,15 @@ __global__ __launch_bounds__(kKnnBlock, (K == 32 ? 3 : 1)) ASP_KNN_OCC void k_kn
             }
         }
     }
-    if (act && !shared && n >= k && diag == 0) {
+    // (x != x: a row without a position -- k_gather -- searches nothing and gets +inf)
+    if (act && !shared && n >= k && diag == 0 && x == x) {
         const double R = sqrt(C.T.mx) * (1.0 + 0x1p-40);
-        int e;
-        frexp(R * G.scale + 1.0, &e);  // cell edge 2^shift >= R + 1 quantum ...
-        const int shift = max(0, min(e, kQBits) - fine), sh3 = 3 * shift;  // ... / 2^fine
+        // cell edge 2^shift >= R + 1 quantum, / 2^fine.  No radius yet (mx = +inf: the window
+        // held fewer than k finite distances): one cell, the whole cube -- R is +inf, so
+        // ca = cb = 0 below, no cell is beyond it, and the lane scans the array minus the
+        // window once
+        const bool whole = !(C.T.mx < INFINITY);
+        const int shift = whole ? kQBits : max(0, ball_level(R * G.scale + 1.0) - fine), sh3 = 3 * shift;
         const double c3[3] = {x, y, z};
         long long ca[3], cb[3];
 #pragma unroll
@@ -1269,7 +1309,8 @@ static int knn(const double* pos, long long n, int k, double* h, int flags, int 
         const int uq = (int)env_int("ASP_KNN_UNION", kUnionQ, 0, 64);
         // ASP_KNN_COUNT: count the distances the search evaluates (bench.py's k-NN roofline;
         // one atomic per lane, so off in timed runs) -> asp_last_stats [9] window, [10] cells,
-        // [11] entries the shared cell pass streamed (once per wave), [12] top-k insertions
+        // [11] entries the shared cell pass streamed (once per wave), [12] top-k insertions,
+        // [8] waves whose shared cell pass fell back to the per-lane pass
         unsigned long long* evc = nullptr;
         if (env_set("ASP_KNN_COUNT")) {
             ASP_TRY(ensure(ws.knn[kKnnCounters], 8 * sizeof(unsigned long long)));
@@ -1313,6 +1354,7 @@ static int knn(const double* pos, long long n, int k, double* h, int flags, int 
             ws.stats[10] = (long long)e[1];
             ws.stats[11] = (long long)e[2];
             ws.stats[12] = (long long)e[3];
+            ws.stats[8] = (long long)e[7];  // waves whose shared cell pass fell back
             if (env_set("ASP_KNN_COUNT_PRINT"))
                 fprintf(stderr, "knn shared pass: %llu waves, %.1f columns and %.1f ranges per wave\n", e[6],
                         e[6] ? (double)e[4] / e[6] : 0.0, e[6] ? (double)e[5] / e[6] : 0.0);

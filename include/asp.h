@@ -354,6 +354,17 @@ int asp_wrapped_distance(const double *from, int64_t pf, const double *to, int64
  * the result is bit-identical to the reference's; +inf when n < k (scipy's value for a
  * missing neighbour).  positions (n, 3) float64 row-major, h float64; 1 <= k <= 64,
  * n < 2^31.  Host pointers unless ASP_F_DEVICE_PTRS (then ordered on `stream`).
+ * Non-finite values (scipy refuses such arrays; here the call is defined): a row with a NaN
+ * or infinite coordinate is nobody's neighbour and gets h = +inf; every other row gets its
+ * k-th smallest finite d2 among the rows with a position, or +inf if fewer than k of its d2
+ * are finite (too few such rows, or squares that overflow: coordinates ~1e160 apart) -- the
+ * value scipy gives on the finite rows alone.  Exact while the finite coordinates' extent
+ * (max - min per axis) is itself finite.  Every thread's work is bounded by n for any input
+ * bits: a particle without a finite k-th distance after its window scans the array once.
+ * Environment (read per call; results do not depend on it): ASP_KNN_WINDOW, ASP_KNN_FINE,
+ * ASP_KNN_F32, ASP_KNN_MASK, ASP_KNN_NEAR, ASP_KNN_FILL, ASP_KNN_UNION, ASP_KNN_SUBMIN
+ * (csrc/asp_knn.hip), ASP_KNN_THREAD (the one-lane-per-particle form, a diagnostic: same
+ * contract), ASP_KNN_COUNT (diagnostic counters: asp_last_stats).
  */
 int asp_knn_smoothing_lengths(const double *positions, int64_t n, int32_t k, double *h,
                               int32_t flags, int32_t device, void *stream);
@@ -578,7 +589,11 @@ int asp_table_interp(const double *table, int32_t ndim, const int32_t *shape,
  * reads the counted pass's records).  Images of more than 4096
  * tiles and batched calls: the sums over all passes.  After asp_knn_smoothing_lengths
  * (ASP_KNN_COUNT) and asp_nearest (ASP_NEAREST_COUNT) the words describe that call: stats[9]
- * = distances evaluated (asp_nearest: over all queries and sets), the map counters 0; after
+ * = distances evaluated (asp_nearest: over all queries and sets), the map counters 0
+ * (asp_knn_smoothing_lengths: stats[9] the window pass's distances, stats[10] the per-lane
+ * cell scans', stats[11] the entries the shared cell pass streamed, stats[12] top-k
+ * insertions, and stats[8] the waves whose shared cell pass fell back to the per-lane pass:
+ * its box of cells, its list of key ranges or its entries beyond what a wave holds); after
  * asp_sample2d(_f64) with ASP_SAMPLE_COUNT stats[9] = (particle, point) pairs tested;
  * after asp_spectra2d(_f64) with it, stats[10] = (pair, bin) adds issued as well.
  */
